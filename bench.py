@@ -12,7 +12,12 @@ collective — SURVEY §8(e) throughput mode).
 
 Data: synthetic — uniformly random RNS residues for ciphertexts and keys, generated on the device
 (RLWE ciphertexts and key-switching keys are pseudo-uniform; every kernel is data-oblivious, so the
-timing equals that of real encryptions; bit-exact parity on real encryptions is in tests/).
+timing equals that of real encryptions; bit-exact parity on real encryptions is in tests/).  The
+seeds are fixed, so the same arguments give the same inputs in every run.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds, after the timed
+steps, the self-check of the timed outputs, the profile step (per-kernel table, roofline), the CPU
+baseline and, at N > 1, the sharded leg.  --dump-outputs DIR writes the last timed step's outputs.
 """
 import argparse
 import json
@@ -91,6 +96,28 @@ def pmc_step_traffic(kernels, B, logn, level, n, variant="ctct"):
                         "source": f"profiles/{tag}_pmc_<kernel>_B{B}{sfx}.json (one PMC step each, FETCH_SIZE x 2 + "
                                   f"WRITE_SIZE; the step's setup dispatches included)"}
     return None
+
+
+DUMP_WORD_BYTES = 60_000_000  # --dump-outputs writes at most this much (the whole directory stays under 64 MB)
+
+
+def dump_outputs(path, words, extras=None):
+    """--dump-outputs: the u64 words of the timed path's outputs (last axis = coefficient) as two float64 arrays,
+    outputs_lo.npy (low 32 bits) and outputs_hi.npy (high 32 bits), so every word survives exactly (the 60-bit
+    prime's residues do not fit a double).  Outputs larger than the budget are sampled at a fixed, seeded set of
+    coefficient positions (coeff_index.npy).  extras: small arrays saved as <name>.npy in float64."""
+    os.makedirs(path, exist_ok=True)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    ncoef = words.shape[-1]
+    fit = max(1, DUMP_WORD_BYTES // (16 * (words.size // ncoef)))
+    if fit < ncoef:
+        idx = np.sort(np.random.default_rng(0).choice(ncoef, fit, replace=False))
+        words = words[..., idx]
+        np.save(os.path.join(path, "coeff_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "outputs_lo.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "outputs_hi.npy"), (words >> np.uint64(32)).astype(np.float64))
+    for name, a in (extras or {}).items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def cgroup_cpu_quota():
@@ -233,6 +260,8 @@ def run_cfg2(args, hec, world, rank, local, barrier, max_over_ranks):
     ctx.synchronize()
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:  # the last timed step's product polynomials
+        dump_outputs(args.dump_outputs, bufs[2].download((npolys, nl, N)))
 
     limb_ntts = 2 * nl * npolys * args.steps * world
     kernels, roof = {}, None
@@ -284,6 +313,7 @@ def run_cfg2(args, hec, world, rank, local, barrier, max_over_ranks):
             "value": round(limb_ntts / dt, 1), "unit": "limb-NTT/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "full": args.full, "dumped_outputs": bool(args.dump_outputs),
             "config": {"workload": f"cfg2: forward NTT + dyadic + inverse NTT of {npolys} polys x {nl} limbs, N=2^15, "
                                    f"primes {{60, 40 x 9}}", "batch_per_gpu": npolys,
                        "parallelism": f"replicas, dp{world}"},
@@ -448,6 +478,16 @@ def main():
                          "without touching a GPU (CPU tests)")
     ap.add_argument("--dry-run-fail", default=None,
                     help="dry run only: inject an exception <prepare|run|selfcheck>:<rank> into the sharded leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the self-check of the "
+                         "timed outputs, the event-timed profile step (per-kernel table, roofline, breakdown), the CPU "
+                         "baseline on the oracle, the HBM probes and, at N > 1, the sharded extra leg.  Without it a run "
+                         "sets up, warms up, times the steps and prints the line (--no-cpu-baseline, --no-profile and "
+                         "--no-self-check switch single parts of --full off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last timed step to DIR as .npy files: the "
+                         "first, middle and last output ciphertext of the batch (cfg2: the product polynomials), every "
+                         "u64 word as two exact float64 halves (outputs_lo.npy, outputs_hi.npy), at most 64 MB")
     args = ap.parse_args()
     wall0 = time.perf_counter()
     if args.config == "cfg5":
@@ -471,6 +511,9 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dry_run:
         return dry_run(args, world, rank)
+    if not args.full:  # a plain run: nothing beside the timed steps
+        args.no_cpu_baseline = args.no_profile = args.no_self_check = True
+        args.sharded_steps = 0
     # torch first, at every N: libhecdna then binds to torch's HIP runtime, so the RCCL buffers and
     # the engine share one runtime and the 1-GPU and N-GPU runs execute the same code
     import torch
@@ -587,6 +630,18 @@ def main():
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     wall["timed_s"] = dt
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        td = time.perf_counter()
+        if sharded:  # rank 0's finished outputs of the last sharded step
+            mine, fin = last_sharded[0]
+            picked = list(zip(mine, fin))[:3]
+        else:
+            picked = [(i, outs[i]) for i in keep]
+        if picked:
+            dump_outputs(args.dump_outputs, np.stack([c.download() for _, c in picked]),
+                         {"batch_index": [i for i, _ in picked], "scales": [c.scale for _, c in picked]})
+        del picked
+        wall["dump_outputs_s"] = time.perf_counter() - td
     hbm = {"total_GB": None, "in_use_after_timed_GB": None, "in_use_max_GB": None}
 
     def hbm_probe(key):
@@ -598,7 +653,8 @@ def main():
         hbm[key] = round(used, 2)
         hbm["in_use_max_GB"] = max(hbm["in_use_max_GB"] or 0.0, round(used, 2))
 
-    hbm_probe("in_use_after_timed_GB")
+    if args.full:
+        hbm_probe("in_use_after_timed_GB")
     tc = time.perf_counter()
 
     # self-check of the timed outputs, after the timer: three outputs of the last timed step (the
@@ -660,11 +716,12 @@ def main():
             lambda f: any_failed_over(dist, f, torch.device("cuda", local)), rank, nsh, args.batch)
         if "plan" in splan_box and "error" not in sharded_extra:
             sharded_extra["key_switches_per_rank"] = [shard.trie_cost(N, p) for p in splan_box["plan"]]
-    if sharded and rank == 0 and last_sharded[0] is not None:
+    if args.full and sharded and rank == 0 and last_sharded[0] is not None:
         sharded_extra = {"self_check": sharded_selfcheck(last_sharded[0], cols)}
 
-    wall["self_check_and_sharded_s"] = time.perf_counter() - tc
-    hbm_probe("in_use_after_checks_GB")
+    if args.full:
+        wall["self_check_and_sharded_s"] = time.perf_counter() - tc
+        hbm_probe("in_use_after_checks_GB")
     if not args.no_profile and prof["where"] is None:
         tp = time.perf_counter()
         profile_step("extra step after the timed steps")
@@ -749,6 +806,7 @@ def main():
             "n_gpus": world, "rccl_world": dist.get_world_size() if dist is not None else 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
             "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "full": args.full, "dumped_outputs": bool(args.dump_outputs),
             "config": {"workload": f"he_linalg BatchedMatrix::matmul diag x col, {args.n}x{args.n} "
                                    f"{'ct x pt' if ctpt else 'ct x ct'} matvec, N=2^{args.logn}, L={L}, "
                                    f"default Galois keys",

@@ -55,6 +55,32 @@ def test_gpus_n_launches_n_ranks_one_line(gpus):
     assert r["n_gpus"] == gpus and r["rccl_world"] == gpus and r["dry_run"] and r["steps"] == 2
 
 
+def test_dump_outputs_exact_halves_and_seeded_sample(bench, tmp_path, monkeypatch):
+    """--dump-outputs: every u64 word comes back exactly from the two float64 halves (60-bit residues do not fit one
+    double); an output above the budget is cut to the same seeded coefficient positions in every run."""
+    import numpy as np
+    words = np.random.default_rng(1).integers(0, 1 << 60, (3, 2, 4, 256), dtype=np.uint64)
+    words[0, 0, 0, :2] = [(1 << 60) - 1, (1 << 53) + 1]
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), words, {"scales": [2.0**40] * 3})
+    lo, hi = np.load(whole / "outputs_lo.npy"), np.load(whole / "outputs_hi.npy")
+    assert lo.dtype == hi.dtype == np.float64 and not (whole / "coeff_index.npy").exists()
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), words)
+    assert np.load(whole / "scales.npy").tolist() == [2.0**40] * 3
+    monkeypatch.setattr(bench, "DUMP_WORD_BYTES", 16 * 24 * 100)  # room for 100 of the 256 positions
+    got = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        bench.dump_outputs(str(d), words)
+        idx = np.load(d / "coeff_index.npy").astype(np.int64)
+        assert len(idx) == 100 and np.all(np.diff(idx) > 0)
+        lo, hi = np.load(d / "outputs_lo.npy"), np.load(d / "outputs_hi.npy")
+        assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), words[..., idx])
+        assert lo.nbytes + hi.nbytes <= 16 * 24 * 100
+        got.append(idx)
+    assert np.array_equal(got[0], got[1])
+
+
 def test_whole_step_pmc_traffic(bench):
     """The line's whole-step PMC figure: the committed round-6 passes at the bench shape sum to the per-kernel traffic
     per matvec (399 GB); a kernel without a pass on that shape, or another shape, gives None rather than

@@ -11,7 +11,7 @@
 set -o pipefail
 TAG=${1:-r03}
 shift
-ARGS="$*"
+ARGS="--full $*"  # the self-check, the profile step and the CPU baseline run only with --full
 DIMS=${PMC_DIMS:-"128 15 10 4096"}
 export PMC_VARIANT=${PMC_VARIANT:-ctct}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG

@@ -1,5 +1,5 @@
-"""rocprofv3 kernel-trace average of the roofline kernel over bench.py's profile step only (development
-tool).  bench.py times its steps (one lane by default since round 5; concurrent lanes with HEC_LANES=3), then runs
+"""rocprofv3 kernel-trace average of the roofline kernel over bench.py --full's profile step only (development
+tool).  bench.py --full times its steps (one lane by default since round 5; concurrent lanes with HEC_LANES=3), then runs
 one extra step as a single lane with HIP event pairs (the roofline's avg_ms), its last GPU work; that step's
 dispatches are the roofline kernel's last `launches_per_step` dispatches in the trace.
 usage: python tools/profile_step.py <run_kernel_trace.csv> <bench.json> <out.json>"""
