@@ -157,6 +157,11 @@ def lib():
             "hec_kswitch_key_load_seal": [vp, vp, C.c_uint64, C.POINTER(vp), u64p],
             "hec_galois_keys_load_seal": [vp, vp, C.c_uint64, u64p],
             "hec_galois_keys_load_seal_ex": [vp, vp, C.c_uint64, C.c_uint64, u64p],
+            "hec_fft_twiddles": [C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+            "hec_bfft_diagonal": [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double)],
+            "hec_fft": [vp, vp, C.c_uint64, C.c_int, vp],
+            "hec_bfft": [vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -396,6 +401,27 @@ def seal_kswitch_keys_load(b: bytes, index, max_bytes=0):
     return out, lists.value, used.value
 
 
+def fft_twiddles(m, inverse=False) -> np.ndarray:
+    """hec_fft_twiddles (host only): the m / 2 complex doubles pow(exp(-+2 pi i / m), k) as the reference's
+    he::fft computes them (libstdc++'s exp and pow), the values hec_fft encodes for block size m."""
+    re, im = np.empty(max(int(m) // 2, 1)), np.empty(max(int(m) // 2, 1))
+    dp = C.POINTER(C.c_double)
+    if lib().hec_fft_twiddles(int(m), int(bool(inverse)), re.ctypes.data_as(dp), im.ctypes.data_as(dp)) != 0:
+        raise InvalidArgument(1, "m must be a power of two >= 2")
+    return np.array([complex(a, b) for a, b in zip(re, im)])  # keeps a -0.0 imaginary part
+
+
+def bfft_diagonal(d, k, n, inverse=False) -> np.ndarray:
+    """hec_bfft_diagonal (host only): the n complex values of diagonal d (0, 1, 2) of the in-slot FFT's stage k = 2^i
+    before tiling over slot_count (reference he_fft.cpp:89-153)."""
+    re, im = np.empty(max(int(n), 1)), np.empty(max(int(n), 1))
+    dp = C.POINTER(C.c_double)
+    if lib().hec_bfft_diagonal(int(d), int(k), int(n), int(bool(inverse)), re.ctypes.data_as(dp),
+                               im.ctypes.data_as(dp)) != 0:
+        raise InvalidArgument(1, "bfft_diagonal: d in {0, 1, 2} (d = 2 needs k > 2), k <= n powers of two")
+    return np.array([complex(a, b) for a, b in zip(re, im)])
+
+
 def create_coeff_modulus(N, bits):
     out = np.zeros(len(bits), dtype=np.uint64)
     _check(lib().hec_create_coeff_modulus(N, (C.c_int * len(bits))(*bits), len(bits), _p(out)))
@@ -588,6 +614,22 @@ class Context:
         out = out or [Ciphertext(self) for _ in accs]
         _check(lib().hec_matmul_finish(self.h, self._arr(accs), len(accs), rk.h, self._arr(out)))
         return out
+
+    # -------------------------------------------------------------- he::fft
+    def fft(self, cts, inverse=False, out=None):
+        """hec_fft: he::fft::fft / ifft over the list of ciphertexts (a power of two of them)."""
+        out = out or [Ciphertext(self) for _ in cts]
+        _check(lib().hec_fft(self.h, self._arr(cts), len(cts), int(bool(inverse)), self._arr(out)))
+        return out
+
+    def bfft(self, cts, n, gk, inverse=False, out=None):
+        """hec_bfft: he::fft::bfft / ibfft with block size n on every ciphertext of the list (or on one
+        ciphertext, then one is returned)."""
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        out = out or [Ciphertext(self) for _ in cts]
+        _check(lib().hec_bfft(self.h, self._arr(cts), len(cts), int(n), int(bool(inverse)), gk.h, self._arr(out)))
+        return out[0] if single else out
 
     def reduce(self, ct):
         """Reduce every word of ct mod its prime (after a partial-sum exchange)."""

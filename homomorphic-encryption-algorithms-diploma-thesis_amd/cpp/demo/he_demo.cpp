@@ -21,6 +21,9 @@
 //                          include/he_util.h:27-77; the chain indices of every output are printed)
 //          least_squares  (src/demos/matrix_operations.cpp:915-1003 on x = c0, y = c1 of 5 data slots: the sums,
 //                          the denominator, signed_inv(denom, 0.05, 6), the numerators, a and b)
+//          fft:<n>[:inv]  (he::fft::fft / ifft over the first <n> input ciphertexts, src/core/he_fft.cpp:70-87)
+//          bfft:<n>[:inv] (he::fft::bfft / ibfft of c0 with block size <n>, src/core/he_fft.cpp:208-223)
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -32,6 +35,7 @@
 #include <string>
 #include <vector>
 
+#include "he_fft.h"
 #include "he_linalg.h"
 #include "he_math.h"
 #include "he_operators.h"
@@ -119,7 +123,7 @@ int main(int argc, char **argv)
 {
     if (argc != 4) {
         std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|"
-                     "util|least_squares|server> <in.bin> <out.bin>\n";
+                     "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|server> <in.bin> <out.bin>\n";
         return 1;
     }
     const std::string mode = argv[1];
@@ -243,6 +247,18 @@ int main(int argc, char **argv)
         keep.push_back(he::math::inv_sqrt_twice(cencd, eval, rk, cts[0], 0.7, iter));
         keep.push_back(he::math::sqrt(ctx, cencd, eval, rk, cts[0], 1.0, iter));
         keep.push_back(he::math::abs(ctx, cencd, eval, rk, cts[1], 1.0, iter));
+    } else if (mode.rfind("fft:", 0) == 0 || mode.rfind("bfft:", 0) == 0) {
+        const bool slot = mode[0] == 'b';
+        const std::string arg = mode.substr(slot ? 5 : 4);
+        const bool inv = arg.size() > 4 && arg.compare(arg.size() - 4, 4, ":inv") == 0;
+        const std::size_t n = std::stoul(arg);
+        hecdna::CKKSEncoder cencd(ctx);
+        if (slot) {
+            keep.push_back(inv ? he::fft::ibfft(cencd, eval, gk, cts[0], n) : he::fft::bfft(cencd, eval, gk, cts[0], n));
+        } else {
+            const std::vector<Ciphertext> vec_ct(cts.begin(), cts.begin() + std::min(n, cts.size()));
+            keep = inv ? he::fft::ifft(cencd, eval, vec_ct) : he::fft::fft(cencd, eval, vec_ct);
+        }
     } else if (mode == "util") {
         hecdna::CKKSEncoder cencd(ctx);
         Ciphertext d0 = cts[0];

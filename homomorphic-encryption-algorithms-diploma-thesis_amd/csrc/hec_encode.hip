@@ -42,13 +42,17 @@ __device__ __forceinline__ void gs(double2 &X, double2 &Y, double2 w)
 // step 1: one thread per slot i of vector blockIdx.y (the work area is zeroed first: SEAL allocates it with 0)
 __global__ void __launch_bounds__(256) k_enc_scatter(const double *__restrict__ re, const double *__restrict__ im,
                                                      u64 nv, const u32 *__restrict__ map, double2 *__restrict__ a,
-                                                     int logN)
+                                                     int logN, u64 period)
 {
     const u64 slots = 1ull << (logN - 1);
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= nv) return;
     const u64 v = blockIdx.y;
-    const double2 z = make_double2(re[v * nv + i], im ? im[v * nv + i] : 0.0);
+    // period < nv: vector v is its first `period` values repeated over the nv slots (period 1: SEAL's
+    // encode(complex<double> value, ...), which fills a slot vector with the value and encodes that; he::fft's
+    // diagonals are n values tiled over slot_count): the same numbers enter the transform as from the full vector
+    const u64 src = v * period + i % period;
+    const double2 z = make_double2(re[src], im ? im[src] : 0.0);
     double2 *av = a + (v << logN);
     av[map[i]] = z;
     av[map[slots + i]] = make_double2(z.x, -z.y);  // std::conj
@@ -157,7 +161,7 @@ __global__ void __launch_bounds__(256) k_enc_finish(const double2 *__restrict__ 
 }  // namespace
 
 void encode_batch(Ctx &c, const double *re, const double *im, u64 nv, int count, double scale, int level, double *work,
-                  u64 *out, u64 *maxabs)
+                  u64 *out, u64 *maxabs, u64 period)
 {
     const int logN = c.logN;
     const u64 N = c.N;
@@ -167,7 +171,8 @@ void encode_batch(Ctx &c, const double *re, const double *im, u64 nv, int count,
     dev_zero(c, maxabs, count * sizeof(u64));
     dev_zero(c, work, (u64)count * N * sizeof(double2));
     if (nv) {
-        k_enc_scatter<<<dim3((unsigned)((nv + 255) / 256), count), 256, 0, c.stream>>>(re, im, nv, c.enc_map, a, logN);
+        k_enc_scatter<<<dim3((unsigned)((nv + 255) / 256), count), 256, 0, c.stream>>>(re, im, nv, c.enc_map, a, logN,
+                                                                                        period ? period : nv);
         HEC_HIP(hipGetLastError());
     }
     const dim3 gl((unsigned)(N >> logc), count);

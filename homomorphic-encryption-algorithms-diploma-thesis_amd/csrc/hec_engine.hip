@@ -2109,31 +2109,38 @@ static u64 exact_residue(double a, u64 q)
     return r;
 }
 
+// SEAL 4.1 CKKSEncoder::encode_internal(double value, parms_id, scale, destination) up to its fill: the checks, in its
+// order, and the word of every limb
+static void scalar_words(const Ctx &c, double value, double scale, std::size_t level, u64 *words)
+{
+    if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    const int total = c.total_bits(level);
+    if (scale <= 0 || (int)std::log2(scale) >= total) throw std::invalid_argument("scale out of bounds");
+    value *= scale;
+    // coeff_bit_count = int(log2 |value|) + 2; a zero value passes (SEAL's cast of -inf), a non-finite one is
+    // rejected (SEAL would cast NaN / inf to int: undefined behaviour)
+    if (!std::isfinite(value)) throw std::invalid_argument("encoded value is too large");
+    if (value != 0.0 && (int)std::log2(std::fabs(value)) + 2 >= total)
+        throw std::invalid_argument("encoded value is too large");
+    const double cd = std::round(value);
+    const bool neg = std::signbit(cd);
+    const double a = std::fabs(cd);
+    for (std::size_t j = 0; j < level; ++j) {
+        const u64 q = c.q[j], r = exact_residue(a, q);
+        words[j] = neg && r ? q - r : r;  // negate_uint_mod
+    }
+}
+
 int hec_encode_scalar(hec_context *ctx, double value, double scale, uint64_t level, hec_plaintext *out)
 {
     return guard([&] {
         need(ctx && out, "null argument");
         Ctx &c = ctx->c;
         set_device(ctx);
-        // SEAL 4.1 CKKSEncoder::encode_internal(double value, parms_id, scale, destination), in its order
         if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
         need(out->ctx == ctx, "plain is not valid for encryption parameters");
-        const int total = c.total_bits(level);
-        if (scale <= 0 || (int)std::log2(scale) >= total) throw std::invalid_argument("scale out of bounds");
-        value *= scale;
-        // coeff_bit_count = int(log2 |value|) + 2; a zero value passes (SEAL's cast of -inf), a non-finite one is
-        // rejected (SEAL would cast NaN / inf to int: undefined behaviour)
-        if (!std::isfinite(value)) throw std::invalid_argument("encoded value is too large");
-        if (value != 0.0 && (int)std::log2(std::fabs(value)) + 2 >= total)
-            throw std::invalid_argument("encoded value is too large");
-        const double cd = std::round(value);
-        const bool neg = std::signbit(cd);
-        const double a = std::fabs(cd);
         u64 words[HEC_MAXL + 1];
-        for (std::size_t j = 0; j < level; ++j) {
-            const u64 q = c.q[j], r = exact_residue(a, q);
-            words[j] = neg && r ? q - r : r;  // negate_uint_mod
-        }
+        scalar_words(c, value, scale, level, words);
         // the constant polynomial in NTT form: every coefficient of limb j is the residue (SEAL's fill_n)
         const std::size_t w = level * c.N;
         if (out->cap < w) {
@@ -2696,6 +2703,286 @@ int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, 
             d2d(c, out[i]->d, O + i * So, So);
             out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = sc[i];
         }
+    });
+}
+
+// ------------------------------------------------------------------ he::fft ----------------
+// Both transforms walk a chain of multiply_plain + rescale stages (reference src/core/he_fft.cpp).  A stage runs over
+// all of its ciphertexts in a fixed number of launches: the stage's plaintexts from the batched encoder, the
+// last-limb products, their batched INTT, the rounding limbs (divide_round's pass A) and the fused
+// multiply-rescale-sum pass (hec_kernels.hip FftIOB); the in-slot FFT adds its two batched rotations.  The twiddles
+// and diagonals come from hec_fft_host.cpp alone.  Outputs are written after the last stage, so an error leaves them
+// untouched.
+namespace {
+constexpr int FFT_MAX_JOBS = 65535;  // blocks along y of one NTT pass
+
+struct FftPlan {
+    std::size_t n = 0, B = 0, l0 = 0;
+    int stages = 0, total = 0;  // total = stages + the inverse's 1/n step
+    double scale = 0;
+    std::vector<double> sc;     // the scale entering step s; sc[total] the result's
+    // the checks shared by hec_fft and hec_bfft: `count` ciphertexts, n the transform size (a class member: no C
+    // language linkage inside the C-ABI block)
+    static FftPlan make(hec_context *ctx, const hec_ciphertext *const *in, uint64_t count, uint64_t n, int inverse,
+                        hec_ciphertext *const *out);
+};
+
+FftPlan FftPlan::make(hec_context *ctx, const hec_ciphertext *const *in, uint64_t count, uint64_t n, int inverse,
+                      hec_ciphertext *const *out)
+{
+    need(ctx && in && out && count >= 1, "null argument");
+    const Ctx &c = ctx->c;
+    need(n >= 1 && !(n & (n - 1)), "n must be a power of two");
+    for (uint64_t i = 0; i < count; ++i) {
+        check_ct(ctx, in[i]);
+        need(out[i] && out[i]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        need(in[i]->size == 2, "encrypted size must be 2");
+        need(in[i]->level == in[0]->level, "encrypted1 and encrypted2 parameter mismatch");
+        need(std::memcmp(&in[i]->scale, &in[0]->scale, sizeof(double)) == 0, "scale mismatch");
+    }
+    FftPlan p;
+    p.n = n;
+    p.l0 = in[0]->level;
+    while ((std::size_t(1) << p.stages) < n) ++p.stages;
+    p.total = p.stages + (inverse ? 1 : 0);
+    if (p.total > 0 && p.l0 < (std::size_t)p.total + 1)
+        throw std::invalid_argument("end of modulus switching chain reached");
+    // every step encodes at the operands' scale and level, multiplies (the scale squares) and rescales
+    double sc = in[0]->scale;
+    p.sc.push_back(sc);
+    for (int s = 0; s < p.total; ++s) {
+        const std::size_t l = p.l0 - s;
+        need(scale_ok(c, sc, l), "scale out of bounds");
+        need(scale_ok(c, sc * sc, l), "scale out of bounds");
+        sc = sc * sc / (double)c.q[l - 1];
+        p.sc.push_back(sc);
+    }
+    return p;
+}
+
+// the encoder's "encoded values are too large" check over the maxima of `count` encoded vectors at `level`
+void fft_check_maxabs(const Ctx &c, const u64 *mx, std::size_t count, std::size_t level)
+{
+    for (std::size_t v = 0; v < count; ++v) {
+        double maxabs;
+        std::memcpy(&maxabs, &mx[v], sizeof(double));
+        if (!std::isfinite(maxabs)) throw std::invalid_argument("encoded values are too large");
+        const int max_bits = (int)std::ceil(std::log2(std::max(maxabs, 1.0))) + 1;
+        if (max_bits >= c.total_bits(level)) throw std::invalid_argument("encoded values are too large");
+    }
+}
+
+// one multiply-rescale-sum stage over source entries W (nsrc entries of 2 polys at level l) -> OUT (nout entries at
+// level l - 1); P = the stage's plaintexts [..][l][N]; half / nb / nt as FftIOB
+void fft_stage_core(Ctx &c, const u64 *W, const u64 *P, u64 *Y, u64 *Z, u64 *OUT, int nsrc, int nout, int l, int half,
+                    int nb, int nt, int npt)
+{
+    const u64 N = c.N, sb = 2 * (u64)l * N, sk = (u64)l * N;
+    {
+        ProfScope k(c, "k:k_fft_lastprod/fft", 4.0 * nsrc + npt);
+        fft_lastprod(c, W, sb, sk, P, sk, Y, nsrc, 2, l, half, nb);
+    }
+    {
+        ProfScope k(c, "k:k_ntt/fft_intt", 8.0 * nsrc, 2);
+        const int pm[1] = {l - 1};
+        ntt_strided(c, true, Y, N, Y, N, 1, pm, 2 * nsrc);
+    }
+    {
+        ProfScope k(c, "k:k_ntt/fft_round_a", 2.0 * nsrc * l);
+        fft_round_limbs(c, Y, Z, nsrc, 2, l);
+    }
+    {  // Z and the source data limbs read once each, the plaintexts' data limbs, the outputs
+        ProfScope k(c, "k:k_ntt/fft_mrs", (4.0 * nsrc + 2.0 * nout + npt) * (l - 1));
+        fft_mrs(c, Z, W, sb, sk, P, sk, PolyArr{OUT, 2 * (u64)(l - 1) * N, (u64)(l - 1) * N}, nout, 2, l, half, nb, nt);
+    }
+}
+
+// the inverse's last step: every entry times the scalar plaintext of 1 / n, rescaled
+void fft_scale_step(Ctx &c, const u64 *W, u64 *P, u64 *Y, u64 *Z, u64 *OUT, int cnt, int l, double n, double scale)
+{
+    u64 words[HEC_MAXL + 1];
+    scalar_words(c, 1.0 / n, scale, (std::size_t)l, words);
+    fill_limbs(c, P, l, words);
+    fft_stage_core(c, W, P, Y, Z, OUT, cnt, cnt, l, 0, cnt, 1, 1);
+}
+
+void fft_store(Ctx &c, const u64 *W, hec_ciphertext *const *out, std::size_t cnt, std::size_t l, double scale)
+{
+    const std::size_t So = 2 * l * c.N;
+    for (std::size_t i = 0; i < cnt; ++i) {
+        ensure(out[i], So);
+        d2d(c, out[i]->d, W + i * So, So);
+        out[i]->size = 2;
+        out[i]->level = l;
+        out[i]->scale = scale;
+    }
+}
+}  // namespace
+
+int hec_fft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t n, int inverse, hec_ciphertext *const *out)
+{
+    return guard([&] {
+        set_device(ctx);
+        const FftPlan p = FftPlan::make(ctx, in, n, n, inverse, out);
+        Ctx &c = ctx->c;
+        const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
+        if (p.total == 0) {  // n = 1 forward: copies
+            if (out[0] != in[0]) {
+                ensure(out[0], S0);
+                d2d(c, out[0]->d, in[0]->d, S0);
+                out[0]->size = 2; out[0]->level = l0; out[0]->scale = in[0]->scale;
+            }
+            return;
+        }
+        need(n * 2 * (l0 - 1) <= (uint64_t)FFT_MAX_JOBS, "too many ciphertexts for one stage");
+        // twiddles of every stage, uploaded once: stage m holds 1 (the identity plaintext) and w_m^k, k < m / 2
+        std::vector<double> tre, tim;
+        for (std::size_t m = 2; m <= n; m <<= 1) {
+            const std::size_t o = tre.size();
+            tre.resize(o + 1 + m / 2);
+            tim.resize(o + 1 + m / 2);
+            tre[o] = 1.0;
+            tim[o] = 0.0;
+            need(hec_fft_twiddles(m, inverse, &tre[o + 1], &tim[o + 1]) == HEC_OK, "n must be a power of two");
+        }
+        const std::size_t ntw = tre.size(), npmax = n / 2 + 1;
+        encoder_tables(c);
+        Scratch s(c, 2 * n * S0 + npmax * l0 * N + 2 * n * N + 2 * n * (l0 - 1) * N + npmax * 2 * N + 3 * ntw +
+                         16 * 64);
+        u64 *Wa = s.take(n * S0), *Wb = s.take(n * S0), *P = s.take(npmax * l0 * N), *Y = s.take(2 * n * N);
+        u64 *Z = s.take(std::max<std::size_t>(2 * n * (l0 - 1) * N, 1));
+        double *work = reinterpret_cast<double *>(s.take(npmax * 2 * N));
+        double *dre = reinterpret_cast<double *>(s.take(ntw)), *dim = reinterpret_cast<double *>(s.take(ntw));
+        u64 *dmx = s.take(ntw);
+        if (ntw) {
+            HEC_HIP(hipMemcpyAsync(dre, tre.data(), ntw * sizeof(double), hipMemcpyHostToDevice, c.stream));
+            HEC_HIP(hipMemcpyAsync(dim, tim.data(), ntw * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        }
+        int lg = 0;
+        while ((std::size_t(1) << lg) < n) ++lg;
+        for (std::size_t j = 0; j < n; ++j)  // the working array: the input in bit-reversed order
+            d2d(c, Wa + j * S0, in[lg ? brev((u32)j, lg) : 0]->d, S0);
+        std::size_t l = l0, off = 0;
+        int step = 0;
+        for (std::size_t m = 2; m <= n; m <<= 1, ++step, --l) {
+            ProfScope ps(c, "fft_stage");
+            const int np = (int)(m / 2 + 1);
+            {
+                ProfScope k(c, "fft_encode");
+                encode_batch(c, dre + off, dim + off, N / 2, np, p.sc[step], (int)l, work, P, dmx + off, 1);
+            }
+            fft_stage_core(c, Wa, P, Y, Z, Wb, (int)n, (int)n, (int)l, (int)(m / 2), 0, 2, np);
+            std::swap(Wa, Wb);
+            off += np;
+        }
+        if (inverse) {
+            ProfScope ps(c, "fft_stage");
+            fft_scale_step(c, Wa, P, Y, Z, Wb, (int)n, (int)l, (double)n, p.sc[step]);
+            std::swap(Wa, Wb);
+            --l;
+        }
+        std::vector<u64> mx(ntw);
+        if (ntw) HEC_HIP(hipMemcpyAsync(mx.data(), dmx, ntw * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        off = 0;
+        for (std::size_t m = 2, ll = l0; m <= n; m <<= 1, --ll) {
+            fft_check_maxabs(c, mx.data() + off, m / 2 + 1, ll);
+            off += m / 2 + 1;
+        }
+        fft_store(c, Wa, out, n, l, p.sc[p.total]);
+    });
+}
+
+int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint64_t n, int inverse,
+             const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    return guard([&] {
+        set_device(ctx);
+        need(n <= ctx->c.N / 2 || (n & (n - 1)), "n must be at most slot_count");
+        const FftPlan p = FftPlan::make(ctx, in, B, n, inverse, out);
+        need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
+        Ctx &c = ctx->c;
+        const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
+        if (p.total == 0) {
+            for (uint64_t i = 0; i < B; ++i)
+                if (out[i] != in[i]) {
+                    ensure(out[i], S0);
+                    d2d(c, out[i]->d, in[i]->d, S0);
+                    out[i]->size = 2; out[i]->level = l0; out[i]->scale = in[i]->scale;
+                }
+            return;
+        }
+        // the rotations of every stage (hec_rotate_vector_inplace's rule: one key, else the NAF terms), found before
+        // any work; diagonals of every stage, n values each, uploaded once
+        std::vector<std::vector<u32>> eltL(p.stages), eltR(p.stages);
+        std::vector<double> dre_h, dim_h;
+        std::vector<int> nterm(p.stages);
+        for (int i = 1; i <= p.stages; ++i) {
+            const uint64_t k = uint64_t(1) << i;
+            const int steps = (int)(n / k);
+            rotation_elts(c, steps, *gk, eltL[i - 1]);
+            if (i > 1) rotation_elts(c, -steps, *gk, eltR[i - 1]);
+            nterm[i - 1] = i > 1 ? 3 : 2;
+            for (int d = 0; d < nterm[i - 1]; ++d) {
+                const std::size_t o = dre_h.size();
+                dre_h.resize(o + n);
+                dim_h.resize(o + n);
+                need(hec_bfft_diagonal(d, k, n, inverse, &dre_h[o], &dim_h[o]) == HEC_OK, "n must be a power of two");
+            }
+        }
+        const std::size_t nd = dre_h.size(), nvec = nd / n;
+        encoder_tables(c);
+        // chunks of ciphertexts: one pass of 3 Bc x 2 x (l0 - 1) blocks
+        const std::size_t Bc = std::min<std::size_t>(B, std::max<std::size_t>(1, FFT_MAX_JOBS / (6 * l0)));
+        Scratch s(c, 6 * Bc * S0 + 3 * l0 * N + 6 * Bc * N + 6 * Bc * (l0 - 1) * N + 3 * 2 * N + 2 * nd + nvec +
+                         ks_words(c, Bc, l0) + 2 * Bc * l0 * N + 16 * 64);
+        u64 *Wa = s.take(3 * Bc * S0), *Wb = s.take(3 * Bc * S0), *P = s.take(3 * l0 * N), *Y = s.take(6 * Bc * N);
+        u64 *Z = s.take(std::max<std::size_t>(6 * Bc * (l0 - 1) * N, 1));
+        double *work = reinterpret_cast<double *>(s.take(3 * 2 * N));
+        double *dre = reinterpret_cast<double *>(s.take(nd)), *dim = reinterpret_cast<double *>(s.take(nd));
+        u64 *dmx = s.take(nvec);
+        HEC_HIP(hipMemcpyAsync(dre, dre_h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        HEC_HIP(hipMemcpyAsync(dim, dim_h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        std::vector<u64> mx(nvec);
+        for (std::size_t b0 = 0; b0 < B; b0 += Bc) {
+            const std::size_t cnt = std::min(Bc, B - b0);
+            for (std::size_t b = 0; b < cnt; ++b) d2d(c, Wa + b * S0, in[b0 + b]->d, S0);
+            std::size_t l = l0, off = 0;
+            for (int i = 1; i <= p.stages; ++i, --l) {
+                ProfScope ps(c, "bfft_stage");
+                const int nt = nterm[i - 1];
+                const u64 sb = 2 * (u64)l * N, sk = (u64)l * N;
+                {
+                    ProfScope k(c, "fft_encode");
+                    encode_batch(c, dre + off * n, dim + off * n, N / 2, nt, p.sc[i - 1], (int)l, work, P, dmx + off, n);
+                }
+                // the two rotations of the batch, back to back: entries [cnt, 2 cnt) and [2 cnt, 3 cnt) of the array
+                const PolyArr X{Wa, sb, sk};
+                for (int t = 1; t < nt; ++t) {
+                    const std::vector<u32> &elts = t == 1 ? eltL[i - 1] : eltR[i - 1];
+                    const PolyArr R{Wa + (u64)t * cnt * sb, sb, sk};
+                    for (std::size_t e = 0; e < elts.size(); ++e)
+                        galois_ks(c, s, e == 0 ? X : R, R, (int)cnt, (int)l, elts[e], gk->keys.at(elts[e]));
+                }
+                fft_stage_core(c, Wa, P, Y, Z, Wb, nt * (int)cnt, (int)cnt, (int)l, 0, (int)cnt, nt, nt);
+                std::swap(Wa, Wb);
+                off += nt;
+            }
+            if (inverse) {
+                ProfScope ps(c, "bfft_stage");
+                fft_scale_step(c, Wa, P, Y, Z, Wb, (int)cnt, (int)l, (double)n, p.sc[p.stages]);
+                std::swap(Wa, Wb);
+                --l;
+            }
+            if (b0 == 0) {
+                HEC_HIP(hipMemcpyAsync(mx.data(), dmx, nvec * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
+                HEC_HIP(hipStreamSynchronize(c.stream));
+                for (std::size_t v = 0, st = 0; st < (std::size_t)p.stages; ++st)
+                    for (int d = 0; d < nterm[st]; ++d, ++v) fft_check_maxabs(c, mx.data() + v, 1, l0 - st);
+            }
+            fft_store(c, Wa, out + b0, cnt, l, p.sc[p.total]);
+        }
+        HEC_HIP(hipStreamSynchronize(c.stream));  // the host diagonals go out of scope
     });
 }
 

@@ -237,8 +237,17 @@ void fill_uniform(Ctx &c, u64 *p, int npoly, int nl, int limb_prime0, int specia
 void fill_limbs(Ctx &c, u64 *p, int nl, const u64 *words);
 // CKKS encode of `count` slot vectors (hec_encode.hip): re/im device [count][nv] (im may be null), work
 // device doubles [count][2N], out [count][level][N] NTT form, maxabs[count] = max |coefficient| (bits
-// of a double)
+// of a double).  period != 0: re/im hold `period` values per vector, repeated over its nv slots (period 1 is the
+// complex-scalar encode he::fft uses for its twiddles, period n its tiled diagonals)
 void encode_batch(Ctx &c, const double *re, const double *im, u64 nv, int count, double scale, int level, double *work,
-                  u64 *out, u64 *maxabs);
+                  u64 *out, u64 *maxabs, u64 period = 0);
+// he::fft stage kernels (hec_kernels.hip, FftIOB): the last-limb products of nsrc source entries with their stage
+// plaintexts, their rounding limbs (divide_round's pass A), and the fused multiply-rescale-sum pass that writes
+// the stage's outputs at level l - 1
+void fft_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_sp, u64 *Y, int nsrc, int nk, int l,
+                  int half, int nb);
+void fft_round_limbs(Ctx &c, const u64 *Y, u64 *Z, int nsrc, int nk, int l);
+void fft_mrs(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_sp, PolyArr OUT, int nout,
+             int nk, int l, int half, int nb, int nt);
 
 }  // namespace hec

@@ -304,6 +304,126 @@ struct DivRoundIOB {
 };
 using DivRoundIO_B = DivRoundIOB<true>;
 
+// The fused multiply-rescale-sum of he::fft (fft_mrs): pass B of the rounding limbs' NTT for one output word of
+//   OUT = sum_t s_t rescale(A_t (*) P_t),  s_t = +-1, 1 to 3 terms,
+// where rescale(X) = (X - NTT(z)) q_last^-1 and z = DivRoundIO_A's rounding limb of X's last limb.  The NTT and the
+// multiplication by q_last^-1 are linear mod q_i and every term's rounding limb z_t is formed from that term's own
+// last limb, so sum_t s_t (A_t P_t - NTT(z_t)) q_last^-1 = (sum_t s_t A_t P_t - NTT(sum_t s_t z_t)) q_last^-1 holds
+// word for word on canonical residues: one pass B per output serves all its terms, and neither a product nor a
+// rescaled operand is stored.  Z holds pass A's output (integer primes: [0, 4q); FP64 primes: integer-valued doubles
+// of magnitude < 10 q), entry (source s, poly k, limb i) at ((s nk + k) nl + i) N.
+// Output entry b takes its terms from the source entries
+//   FFT stage (half = m / 2): e = (b & ~(m - 1)) + (b & (half - 1)), o = e + half, plaintexts 0 and 1 + (b & (half - 1)),
+//                             the second term subtracted when b & half;
+//   in-slot stage (half = 0): entries t nb + b (t = 0 the ciphertext, 1 / 2 its two rotations), plaintext t.
+struct FftIOB {
+    const u64 *Z, *A, *P;
+    u64 a_sb, a_sk, p_sp;  // source entry / poly strides, plaintext stride (limb stride N)
+    PolyArr OUT;
+    int nk, nl, logN, half, nb, nt;
+    const DevPrime *primes;
+    u64 inv[HEC_MAXL], inv_q[HEC_MAXL];
+    struct Bound {
+        static constexpr bool kFpStore = true;
+        static constexpr bool kLatePre = true;  // the operands are loaded at the store: one word per output in flight
+        const u64 *z[3], *a[3], *p[3];
+        u64 *out;
+        int nt;
+        bool neg;  // the second term is subtracted
+        DevPrime pr;
+        u64 w, wq;
+        int prime;
+        bool fpstore = true;
+        bool valid = true;
+        struct Pre {
+            u64 x;  // sum_t s_t a_t p_t mod q, canonical
+        };
+        __device__ Pre pre(u64 g) const
+        {
+            u64 av[3], pv[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+                if (t < nt) { av[t] = a[t][g]; pv[t] = p[t][g]; }
+            if (pr.fp) {
+                double s = fp_mulmod(u2d(av[0]), u2d(pv[0]), pr.qd, pr.qinv);
+                if (nt >= 2) {
+                    const double s1 = fp_mulmod(u2d(av[1]), u2d(pv[1]), pr.qd, pr.qinv);
+                    s = neg ? s - s1 : s + s1;
+                }
+                if (nt == 3) s += fp_mulmod(u2d(av[2]), u2d(pv[2]), pr.qd, pr.qinv);
+                return Pre{fp_canon(s, pr.qd, pr.qinv)};  // |s| < 1.6 q
+            }
+            u64 s = mulmod(av[0], pv[0], pr);
+            if (nt >= 2) {
+                const u64 s1 = mulmod(av[1], pv[1], pr);
+                s = neg ? submod(s, s1, pr.q) : addmod(s, s1, pr.q);
+            }
+            if (nt == 3) s = addmod(s, mulmod(av[2], pv[2], pr), pr.q);
+            return Pre{s};
+        }
+        // sum_t s_t z_t in the butterflies' input range
+        __device__ u64 load(u64 g) const
+        {
+            if (pr.fp) {
+                double s = __longlong_as_double((long long)z[0][g]);
+                if (nt >= 2) {
+                    const double s1 = __longlong_as_double((long long)z[1][g]);
+                    s = neg ? s - s1 : s + s1;
+                }
+                if (nt == 3) s += __longlong_as_double((long long)z[2][g]);
+                return (u64)__double_as_longlong(fp_reduce(s, pr.qd, pr.qinv));  // |s| < 30 q -> [-0.53 q, 0.53 q]
+            }
+            const u64 two_q = 2 * pr.q;
+            u64 s = csub(z[0][g], two_q);
+            if (nt >= 2) {
+                const u64 s1 = csub(z[1][g], two_q);
+                s = neg ? s + two_q - s1 : s + s1;  // [0, 4q)
+            }
+            if (nt == 3) s = csub(s + csub(z[2][g], two_q), 2 * two_q);  // [0, 6q) -> [0, 4q)
+            return s;
+        }
+        __device__ void store(u64 g, u64 v, Pre p) const
+        {
+            st1m<2>(out + g, shoup(p.x + pr.q - v, w, wq, pr.q));
+        }
+        __device__ void store_fp(u64 g, double v, Pre p, const DevPrime &) const
+        {
+            const double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv);
+            st1m<2>(out + g, fp_canon(r, pr.qd, pr.qinv));
+        }
+    };
+    __device__ Bound bind(int job) const
+    {
+        const int i = job % nl, t = job / nl, k = t % nk, b = t / nk;
+        const u64 li = (u64)i << logN;
+        Bound bo;
+        int src[3], pt[3];
+        if (half) {
+            const int kk = b & (half - 1);
+            src[0] = (b & ~(2 * half - 1)) + kk;
+            src[1] = src[0] + half;
+            src[2] = 0;
+            pt[0] = 0; pt[1] = 1 + kk; pt[2] = 0;
+            bo.neg = (b & half) != 0;
+        } else {
+            for (int s = 0; s < 3; ++s) { src[s] = s < nt ? s * nb + b : b; pt[s] = s < nt ? s : 0; }
+            bo.neg = false;
+        }
+        for (int s = 0; s < 3; ++s) {
+            bo.z[s] = Z + ((u64)((src[s] * nk + k) * nl + i) << logN);
+            bo.a[s] = A + (u64)src[s] * a_sb + (u64)k * a_sk + li;
+            bo.p[s] = P + (u64)pt[s] * p_sp + li;
+        }
+        bo.out = OUT.p + b * OUT.sb + k * OUT.sk + li;
+        bo.nt = nt;
+        bo.pr = primes[i];
+        bo.w = inv[i];
+        bo.wq = inv_q[i];
+        bo.prime = i;
+        return bo;
+    }
+};
+
 // =============================================================================== NTT core ==
 // Twiddle tables per prime: integer {w, w_shoup} pairs (60-bit primes) and integer-valued doubles
 // (primes < 2^42, FP64 arithmetic), each in SEAL order for pass A and re-laid for pass B.
@@ -1124,6 +1244,66 @@ void divide_round(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, PolyArr X, PolyArr IN,
     };
     if (IN.p != nullptr && in_nk > 0) run(DivRoundIOB<true>{});
     else run(DivRoundIOB<false>{});
+}
+
+// he::fft stage kernels.  The plaintext of source entry s: FFT stage (half = m / 2) entry offset o = s & (m - 1) takes
+// plaintext 0 (the encoded 1) when o < half, else 1 + o - half (the encoded w^k); in-slot stage (half = 0) s / nb.
+// Y[(s nk + k)][g] = A[s][k][last][g] P[pt(s)][last][g] mod q_last: the last-limb products, the only part of a
+// product the divide-and-round needs ahead of the fused pass.
+__global__ void __launch_bounds__(256)
+    k_fft_lastprod(const u64 *__restrict__ A, u64 a_sb, u64 a_sk, const u64 *__restrict__ P, u64 p_sp,
+                   u64 *__restrict__ Y, int nk, int logN, int half, int nb, int last, u64 total,
+                   const DevPrime *__restrict__ primes)
+{
+    const u64 idx = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const u64 g = idx & ((1ull << logN) - 1), t = idx >> logN;
+    const int k = (int)(t % nk), s = (int)(t / nk);
+    int pt;
+    if (half) {
+        const int o = s & (2 * half - 1);
+        pt = o < half ? 0 : 1 + o - half;
+    } else {
+        pt = s / nb;
+    }
+    const u64 lo = (u64)last << logN;
+    const DevPrime pr = primes[last];
+    Y[idx] = mulmod(A[(u64)s * a_sb + (u64)k * a_sk + lo + g], P[(u64)pt * p_sp + lo + g], pr);
+}
+
+void fft_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_sp, u64 *Y, int nsrc, int nk, int l,
+                  int half, int nb)
+{
+    const u64 total = (u64)nsrc * nk * c.N;
+    k_fft_lastprod<<<(unsigned)((total + 255) / 256), 256, 0, c.stream>>>(A, a_sb, a_sk, P, p_sp, Y, nk, c.logN, half,
+                                                                         nb, l - 1, total, c.primes);
+    HEC_HIP(hipGetLastError());
+}
+
+// the rounding limbs of nsrc x nk coefficient-form last limbs Y (divide_round's pass A), Z as FftIOB reads it
+void fft_round_limbs(Ctx &c, const u64 *Y, u64 *Z, int nsrc, int nk, int l)
+{
+    const int nl = l - 1;
+    if (nl > HEC_MAXL) throw std::invalid_argument("too many limbs");
+    DivRoundIO_A a{};
+    a.Y = Y; a.ysb = (u64)nk * c.N; a.ysk = c.N; a.Z = Z; a.nk = nk; a.nl = nl; a.logN = c.logN;
+    a.last = c.q[l - 1]; a.half = a.last >> 1; a.primes = c.primes;
+    for (int i = 0; i < nl; ++i) a.fix[i] = c.q[i] - (a.half % c.q[i]);
+    ntt_dispatch<false>(c, nsrc * nk * nl, a, DivRoundIOB<false>{}, 1);
+}
+
+// the fused pass (FftIOB): nout output entries of nk polys at level l - 1
+void fft_mrs(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_sp, PolyArr OUT, int nout,
+             int nk, int l, int half, int nb, int nt)
+{
+    const int nl = l - 1;
+    if (nl > HEC_MAXL) throw std::invalid_argument("too many limbs");
+    if (nt < 1 || nt > 3) throw std::invalid_argument("fft_mrs: 1 to 3 terms");
+    FftIOB b{};
+    b.Z = Z; b.A = A; b.P = P; b.a_sb = a_sb; b.a_sk = a_sk; b.p_sp = p_sp; b.OUT = OUT;
+    b.nk = nk; b.nl = nl; b.logN = c.logN; b.half = half; b.nb = nb; b.nt = nt; b.primes = c.primes;
+    for (int i = 0; i < nl; ++i) { b.inv[i] = c.ql_inv[l][i]; b.inv_q[i] = c.ql_inv_q[l][i]; }
+    ntt_dispatch<false>(c, nout * nk * nl, DivRoundIO_A{}, b, 2);
 }
 
 // =============================================================== fan-out: INTT pass A -> fwd passes A ==

@@ -204,6 +204,34 @@ int hec_matrix_matmul(hec_context *ctx, const hec_ciphertext *const *A, uint64_t
                       int a_transposed, const hec_ciphertext *const *B, uint64_t b_rows, uint64_t b_cols,
                       int b_transposed, const hec_kswitch_key *rk, hec_ciphertext *const *out);
 
+/* ---------------------------------------------------------------- he::fft ------------------ */
+/* The doubles he::fft encodes (reference src/core/he_fft.cpp:40,55 and :92-149), host only, no device: the one
+ * source of these values for the engine, the C++ drop-in and the tests (libstdc++'s std::exp and
+ * std::pow(complex<double>, size_t), which is not the repeated product; entry 0 is (1, -0)).
+ * hec_fft_twiddles: re/im[k] = pow(exp(i s (-2 pi) / m), k) for k < m / 2, s = +1 forward, -1 inverse; m a power of
+ * two >= 2.  hec_bfft_diagonal: the n values of diag_D<s>(d, k, n) before it is tiled over slot_count, d in {0, 1, 2}
+ * (d = 2 needs k > 2), k = 2^i <= n.  HEC_EINVAL for arguments outside these ranges (no message is recorded). */
+int hec_fft_twiddles(uint64_t m, int inverse, double *re, double *im);
+int hec_bfft_diagonal(int d, uint64_t k, uint64_t n, int inverse, double *re, double *im);
+/* he::fft::fft / ifft (he_fft.cpp:13-87): the radix-2 FFT over n ciphertexts, out[j] = sum_i in[i] w_n^(i j).
+ * Every butterfly of block size m is E = rescale(e (*) encode(1 + 0i)), T = rescale(o (*) encode(w_m^k)), E + T and
+ * E - T, the plaintexts complex-scalar encodes at the operands' level and scale; ifft multiplies every output by
+ * the scalar encode of 1.0 / n and rescales once more.  A stage runs over all n ciphertexts at once.  n a power
+ * of two ("n must be a power of two"; the reference does not check); every in[i] of size 2 ("encrypted size must be
+ * 2"), at one level ("encrypted1 and encrypted2 parameter mismatch") with bitwise-equal scales ("scale mismatch");
+ * level >= log2 n + 1, one more for the inverse ("end of modulus switching chain reached"); "scale out of bounds"
+ * where a multiply_plain of the chain would throw it.  Nothing is written on an error.  out[i] may be a fresh
+ * handle or in[i]; n = 1 forward copies.  n * 2 * (level - 1) <= 65535. */
+int hec_fft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t n, int inverse, hec_ciphertext *const *out);
+/* he::fft::bfft / ibfft (he_fft.cpp:166-223) on B independent ciphertexts whose slot vectors are n-periodic (B = 1
+ * is the reference's call): for i = 1 .. log2 n, k = 2^i, steps = n / k,
+ *   y = rescale(y (*) D0) + rescale(rot(y, +steps) (*) D1) [+ rescale(rot(y, -steps) (*) D2) for i > 1],
+ * the diagonals hec_bfft_diagonal's values tiled over slot_count; ibfft adds the 1.0 / n step.  Each n-block of
+ * the result is its DFT in bit-reversed order.  Rotations as hec_rotate_vector_inplace (one key for +-steps, else the
+ * NAF terms; "Galois key not present").  Errors as hec_fft, and n <= slot_count ("n must be at most slot_count"). */
+int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint64_t n, int inverse,
+             const hec_galois_keys *gk, hec_ciphertext *const *out);
+
 /* ---------------------------------------------------------------- multi-GPU (SURVEY 8(b),(e)) */
 /* One process per GPU.  The reference is single-threaded (no collective anywhere); the sharded matvec splits
  * the diagonal loop of BatchedMatrix::matmul (he_linalg.cpp:977-997) over the ranks and exchanges the size-3
