@@ -499,6 +499,35 @@ void keyswitch(Ctx &c, Scratch &s, PolyArr T, const u64 *key, PolyArr IN, int in
             if (fan) fan_modup(c, D, E, B, l);
             else ks_modup_mac(c, D, E, T, key, ACC, B, l, 1, elt);
         }
+        if (fan && c.mac_divround && !(c.moddown1 && c.logN == 15)) {
+            // the special-prime target first; its INTT and the fan-out give the rounding limbs Z, and the data
+            // targets' launch divides-and-rounds its accumulators in its epilogue: ACC's data limbs are never stored
+            const int pP[1] = {(int)c.K - 1};
+            {  // digits E[b][P] (B l) + key (2 l) -> ACC's P limbs (2 B)
+                ProfScope ps(c, "ks_bmac");
+                ProfScope k(c, "k:k_bmac/p", (double)B * l + 2.0 * l + 2.0 * B, 1);
+                ks_modup_mac(c, D, E, T, key, ACC, B, l, 2, elt, nullptr, 1);
+            }
+            {
+                ProfScope ps(c, "ks_moddown");
+                {
+                    ProfScope k(c, "k:k_ntt/moddown_intt", 4.0 * B, 1);
+                    ntt_strided(c, true, ACC + l * N, (l + 1) * N, ACC + l * N, (l + 1) * N, 1, pP, 2 * B, 1, 1);
+                }
+                ProfScope k(c, "k:k_fan2/moddown", 2.0 * B * (l + 1));
+                fan_divide_round(c, ACC + l * N, 2 * (l + 1) * N, (l + 1) * N, Z, B, 2, l, (int)c.K - 1);
+            }
+            {  // digits E (B l (l - 1)) + targets (B l) + key (2 l l) + Z (2 B l) + IN (in_nk B l) -> OUT (2 B l)
+                ProfScope ps(c, "ks_bmac");
+                ProfScope k(c, "k:k_bmac/divround", (double)B * l * l + 2.0 * l * l + (4.0 + in_nk) * B * l, 1);
+                BmacDR dr{};
+                dr.Z = Z; dr.IN = IN; dr.OUT = OUT; dr.in_nk = in_nk;
+                for (int i = 0; i < l; ++i) { dr.inv[i] = c.p_inv[i]; dr.inv_q[i] = c.p_inv_q[i]; }
+                ks_modup_mac(c, D, E, T, key, ACC, B, l, 2, elt, &dr, 2);
+            }
+            s.top = top;
+            return;
+        }
         {  // digits E (B l^2) + the I == J targets (B l) + key (2 l K) -> ACC (2 B K)
             ProfScope ps(c, "ks_bmac");
             ProfScope k(c, "k:k_bmac", (double)B * l * l + (double)B * l + 2.0 * l * K + 2.0 * B * K,
@@ -1469,10 +1498,18 @@ int hec_context_create(uint64_t N, const uint64_t *mod, uint64_t K, int device, 
             need(isprime(mod[i]) && (mod[i] - 1) % (2 * N) == 0 && !(mod[i] >> 60), "coeff_modulus is invalid");
         for (uint64_t i = 0; i < K; ++i)
             for (uint64_t j = 0; j < i; ++j) need(mod[i] != mod[j], "coeff_modulus is invalid");
+        int mac_divround = -1;
+        if (const char *f = std::getenv("HEC_MAC_DIVROUND")) {  // an A/B value outside the range must not pass
+            char *end = nullptr;
+            const long v = std::strtol(f, &end, 10);
+            need(end != f && *end == 0 && v >= 0 && v <= 1, "HEC_MAC_DIVROUND takes 0..1");
+            mac_divround = (int)v;
+        }
         HEC_HIP(hipSetDevice(device));
         auto *ctx = new hec_context();
         Ctx &c = ctx->c;
         c.device = device;
+        if (mac_divround >= 0) c.mac_divround = mac_divround;
         if (const char *f = std::getenv("HEC_FUSED_MODUP_MAC")) c.fused_modup_mac = f[0] != '0';
         if (const char *f = std::getenv("HEC_FUSE_GALOIS")) c.fuse_galois = f[0] != '0';
         if (const char *f = std::getenv("HEC_FAN")) c.fan_out = f[0] != '0';
@@ -1586,15 +1623,22 @@ int hec_context_create(uint64_t N, const uint64_t *mod, uint64_t K, int device, 
             HEC_HIP(hipMemset(c.zflag, 0, 2 * sizeof(int)));
         }
         {   // target-prime order tables per level (integer primes first)
-            std::vector<int> tab((c.L + 1) * (HEC_MAXL + 2), 0);
+            // second half (imap_split_at): row l = {l, then the data targets, integer primes first}
+            std::vector<int> tab(2 * (c.L + 1) * (HEC_MAXL + 2), 0);
             c.imap_nint.assign(c.L + 1, 0);
+            c.imap_pint = c.hprimes[K - 1].fp ? 0 : 1;
             for (std::size_t l = 1; l <= c.L; ++l) {
                 int *t = tab.data() + l * (HEC_MAXL + 2), n = 0;
+                int *t2 = tab.data() + (c.L + 1 + l) * (HEC_MAXL + 2), n2 = 0;
+                t2[n2++] = (int)l;
                 for (int pass = 0; pass < 2; ++pass)
                     for (int I = 0; I <= (int)l; ++I) {
                         const int kI = I == (int)l ? (int)K - 1 : I;
                         const bool fp = c.hprimes[kI].fp != 0;
-                        if ((pass == 0) != fp) t[n++] = I;
+                        if ((pass == 0) != fp) {
+                            t[n++] = I;
+                            if (I != (int)l) t2[n2++] = I;
+                        }
                     }
                 for (int I = 0; I <= (int)l; ++I)
                     if (!c.hprimes[I == (int)l ? K - 1 : I].fp) ++c.imap_nint[l];
@@ -1725,6 +1769,7 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "moddown1") c.moddown1 = in(0, 1);
             else if (n == "nt_e") c.nt_e = in(0, 1);
             else if (n == "bmac_split") c.bmac_split = value != 0;
+            else if (n == "mac_divround") c.mac_divround = in(0, 1);
             else if (n == "hoist") c.hoist = value != 0;
             else if (n == "hoist_min") c.hoist_min_children = (int)std::max<int64_t>(1, value);
             else if (n == "hmac") c.hmac_cfg = in(0, 2);

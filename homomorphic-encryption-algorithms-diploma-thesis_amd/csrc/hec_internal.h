@@ -82,6 +82,15 @@ struct Ctx {
     int *imap = nullptr;
     std::vector<int> imap_nint;
     const int *imap_at(int l) const { return imap + (std::size_t)l * (HEC_MAXL + 2); }
+    // the same table's second half, for the key MAC split by target (mac_divround): row l = {l (P), then the data
+    // targets I in [0, l), integer primes first}; imap_pint: P is an integer-arithmetic prime
+    const int *imap_split_at(int l) const { return imap + (L + 1 + (std::size_t)l) * (HEC_MAXL + 2); }
+    int imap_pint = 0;
+    // HEC_MAC_DIVROUND / option "mac_divround": 1 the per-rotation key switch accumulates the special-prime target
+    // first, runs the P-limb INTT and the fan-out, and the data targets' k_bmac launch divides-and-rounds its own
+    // accumulators in an epilogue (no ACC data limbs in memory, no divide-and-round pass B launch); 0 the separate
+    // pass B.  Applies with fan_out && fused_modup_mac && !moddown1
+    int mac_divround = 1;
     // hoisted mod-up (see hec_kernels.hip): psi_i^e for e in [0, 2N) per key prime, c[J][I] = q_J mod q_I,
     // and a device flag raised when a digit limb holds more zero coefficients than the kernels correct
     u64 *psipow = nullptr;
@@ -157,8 +166,18 @@ void ks_modup(Ctx &c, const u64 *D, u64 *E, int B, int l, int stages = 3,
 void ks_mac(Ctx &c, PolyArr T, const u64 *E, const u64 *key, u64 *ACC, int B, int l, u32 elt);
 // fused: pass A of the mod-up NTTs (part & 1), then (pass B + key MAC) per target prime -> ACC[b][k][I]
 // (part & 2)
+// dr == nullptr: one launch over every target I in [0, l].  Otherwise part 2 is one of two launches: tsel 1 the
+// special-prime target alone -> ACC[b][k][l]; tsel 2 the data targets, whose blocks run pass B of their chunks of the
+// rounding limbs Z (fan_divide_round's output) and store OUT = (acc - NTT(z)) P^-1 (+ IN through elt for polys
+// k < in_nk) instead of ACC.  A block reads IN only at the words it writes, so IN may be OUT.
+struct BmacDR {
+    const u64 *Z;
+    PolyArr IN, OUT;
+    int in_nk;
+    u64 inv[HEC_MAXL], inv_q[HEC_MAXL];  // P^-1 mod q_i and its Shoup quotient
+};
 void ks_modup_mac(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l, int part,
-                  u32 elt);
+                  u32 elt, const BmacDR *dr = nullptr, int tsel = 0);
 // divide-and-round by `last_idx` prime: Y = coefficient-form last limb per (b,k) (address Y + b*ysb + k*ysk),
 // X / IN / OUT addressed (b,k,i), nk polys per batch entry, nl output limbs.
 //   OUT = IN + (X - NTT(corr)) * inv   (IN optional; inv = last^-1 mod q_i)

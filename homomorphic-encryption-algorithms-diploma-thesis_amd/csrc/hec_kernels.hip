@@ -2840,12 +2840,24 @@ __device__ __forceinline__ void ntt_round_x(u64 *row, int ts, const TwG &twg, co
     }
 }
 
+// The divide-and-round epilogue's operands of one (b, I) (BmacDR resolved per block): the limbs of Z, IN (null: no IN
+// term for that poly) and OUT of polys k = 0, 1, and P^-1 mod q_I with its Shoup quotient
+struct BmacDRB {
+    const u64 *z[2], *in[2];
+    u64 *out[2];
+    u64 w, wq;
+};
+
 // SPL (integer targets): the pass-B butterflies as split-input Shoup, their extra twiddle words staged in ltwa
-template <int LOGP, int NSEG, int EPT, bool FP, bool SPL = false>
+// DR (data targets, mac_divround): instead of storing the accumulators, the block runs pass B of its chunks of the
+// mod-down's rounding limbs Z (the same chunks, twiddles and rounds as a digit tile) and stores
+// OUT = (acc - NTT(z)) P^-1 (+ IN), what the divide-and-round pass B computes from ACC: the same exact arithmetic on
+// canonical residues, so the same words.  IN is read only at the words the thread writes (IN may be OUT).
+template <int LOGP, int NSEG, int EPT, bool FP, bool SPL = false, bool DR = false>
 __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr T, const u64 *__restrict__ E,
                                           const u64 *__restrict__ key,
                                           u64 *__restrict__ ACC, const TwTables &tt, const DevPrime &pr, int I, int kI,
-                                          int b, int xb, int logN, int l, int K, u32 elt)
+                                          int b, int xb, int logN, int l, int K, u32 elt, const BmacDRB &dr = BmacDRB{})
 {
     // segment-major lane layout: the P / EPT threads of one chunk are consecutive lanes.  At P = 128 and 256 (the
     // cfg3 / cfg5 sizes) a chunk row is exactly P words with the XOR swizzle of BSwz (element x at word x ^ f(x),
@@ -2925,6 +2937,25 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
     };
     constexpr bool SWZ = BSwz<LOGP>::on;
     u64 *const row = lds + sg * LD;
+    auto rounds = [&](const auto &twg, u64 *v) {
+        static_assert(LOGP >= 5 && LOGP <= 8, "pass-B sizes 2^5 .. 2^8");
+        static_assert(EPT == 4, "rounds of 2 stages");
+        if constexpr (SWZ) {
+            ntt_round_x<LOGP, 0, 2, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 2, 4, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 4, 6, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 6, LOGP, EPT, false, FP, true>(row, ts, twg, pr, v);
+        } else if constexpr (LOGP <= 6) {
+            ntt_round_g<LOGP, 0, 2, EPT, false, FP, false>(lds, addr, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_g<LOGP, 2, 4, EPT, false, FP, false>(lds, addr, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_g<LOGP, 4, LOGP, EPT, false, FP, true>(lds, addr, ts, twg, pr, v);
+        }
+    };
     load_tile(0);
     for (int J = 0; J < l; ++J) {
         const bool ntt = J != I;
@@ -2952,28 +2983,9 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
         if (J + 1 < l) load_tile(J + 1);
         __syncthreads();
         u64 v[EPT];
-        auto rounds = [&](const auto &twg) {
-            static_assert(LOGP >= 5 && LOGP <= 8, "pass-B sizes 2^5 .. 2^8");
-            static_assert(EPT == 4, "rounds of 2 stages");
-            if constexpr (SWZ) {
-                ntt_round_x<LOGP, 0, 2, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
-                __syncthreads();
-                ntt_round_x<LOGP, 2, 4, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
-                __syncthreads();
-                ntt_round_x<LOGP, 4, 6, EPT, false, FP, false>(row, ts, twg, pr, nullptr);
-                __syncthreads();
-                ntt_round_x<LOGP, 6, LOGP, EPT, false, FP, true>(row, ts, twg, pr, v);
-            } else if constexpr (LOGP <= 6) {
-                ntt_round_g<LOGP, 0, 2, EPT, false, FP, false>(lds, addr, ts, twg, pr, nullptr);
-                __syncthreads();
-                ntt_round_g<LOGP, 2, 4, EPT, false, FP, false>(lds, addr, ts, twg, pr, nullptr);
-                __syncthreads();
-                ntt_round_g<LOGP, 4, LOGP, EPT, false, FP, true>(lds, addr, ts, twg, pr, v);
-            }
-        };
         if (ntt) {
-            if constexpr (!FP && SPL) rounds(twgs);
-            else rounds(twg0);
+            if constexpr (!FP && SPL) rounds(twgs, v);
+            else rounds(twg0, v);
         } else if constexpr (SWZ) {
             const int xb = bswz<LOGP>(ts * EPT);
 #pragma unroll
@@ -2999,6 +3011,77 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
         }
         __syncthreads();
     }
+    if constexpr (DR) {
+        // the digit loop's last barrier freed the chunk rows.  Per poly k: the Z tile is staged like a digit tile (FP64
+        // primes: pass A stored integer-valued doubles), the rounds leave NTT(z) of the thread's outputs in v
+        // (integers < 4q; FP64 |v| < 10q), and the post-op is DivRoundIOB's.  The FP64 sum (|acc| <= 0.53 q l) is
+        // reduced to [-0.53q, 0.53q] first, so fp_mulmod's operand stays below 10.53q (store_fp's own bound is 11q)
+        const u64 two_q = 2 * pr.q;
+        auto load_z = [&](int k) {
+            const ulonglong2 *sp = (const ulonglong2 *)(dr.z[k] + base);
+#pragma unroll
+            for (int e = 0; e < EPT / 2; ++e) {
+                const ulonglong2 w = sp[threadIdx.x + e * THREADS];
+                nx[2 * e] = w.x;
+                nx[2 * e + 1] = w.y;
+            }
+        };
+        auto poly = [&](int k, auto *acc) {
+#pragma unroll
+            for (int e = 0; e < EPT; e += 2) {
+                const int li = 2 * (threadIdx.x + (e / 2) * THREADS);
+                if constexpr (SWZ) {
+                    *(ulonglong2 *)(lds + (li / P) * LD + bswz<LOGP>(li % P)) = ulonglong2{nx[e], nx[e + 1]};
+                } else {
+                    lds[(li / P) * LD + (li % P) + ((li % P) >> 4)] = nx[e];
+                    lds[(li / P) * LD + (li % P) + 1 + (((li % P) + 1) >> 4)] = nx[e + 1];
+                }
+            }
+            if (k == 0) load_z(1);
+            u64 in[EPT];
+            const u64 *ip = dr.in[k];
+            if (ip) {  // block-uniform
+#pragma unroll
+                for (int e = 0; e < EPT; e += 2) {
+                    const u32 t = elt == 1 ? (u32)(g0 + e) : galois_src((u32)(g0 + e), elt, logN);
+                    const ulonglong2 w = *(const ulonglong2 *)(ip + (t & ~1u));
+                    in[e] = (t & 1) ? w.y : w.x;
+                    in[e + 1] = (t & 1) ? w.x : w.y;
+                }
+            }
+            __syncthreads();
+            u64 v[EPT];
+            if constexpr (!FP && SPL) rounds(twgs, v);
+            else rounds(twg0, v);
+            u64 r[EPT];
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) {
+                if constexpr (FP) {
+                    const double x = fp_reduce(acc[e], pr.qd, pr.qinv);
+                    double y = fp_mulmod(x - __longlong_as_double((long long)v[e]), u2d(dr.w), pr.qd, pr.qinv);
+                    if (ip) y += u2d(in[e]);
+                    r[e] = fp_canon(y, pr.qd, pr.qinv);
+                } else {
+                    const u64 x = barrett128(acc[e].lo, acc[e].hi, pr.q, pr.r0, pr.r1);
+                    const u64 z = csub(csub(v[e], two_q), pr.q);
+                    r[e] = shoup(x + pr.q - z, dr.w, dr.wq, pr.q);
+                    if (ip) r[e] = addmod(r[e], in[e], pr.q);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < EPT; e += 2) st2m<2>(dr.out[k] + g0 + e, ulonglong2{r[e], r[e + 1]});
+            if (k == 0) __syncthreads();  // the rows are staged again
+        };
+        load_z(0);
+        if constexpr (FP) {
+            poly(0, f0);
+            poly(1, f1);
+        } else {
+            poly(0, i0);
+            poly(1, i1);
+        }
+        return;
+    }
     u64 *o0 = ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + g0;
     u64 *o1 = ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + g0;
 #pragma unroll
@@ -3017,11 +3100,13 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
 
 // one launch: Imap lists every target prime, the first nint integer ones (per-block branch; blocks of both
 // kinds overlap)
-template <int LOGP, int NSEG, int EPT, bool SPL>
+// DRA = one BmacDR: the data targets' launch with the divide-and-round epilogue (Imap lists data primes only; ACC
+// unused); no DRA: the accumulators go to ACC
+template <int LOGP, int NSEG, int EPT, bool SPL, class... DRA>
 __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SIMD (<= 128 VGPRs), as without SPL
     k_bmac(PolyArr T, const u64 *__restrict__ E, const u64 *__restrict__ key, u64 *__restrict__ ACC, TwTables tt,
            const DevPrime *__restrict__ primes, const int *__restrict__ Imap, int nI, int logN, int l, int K,
-           int nint, int gpad, u32 elt)
+           int nint, int gpad, u32 elt, const DRA... dra)
 {
     __shared__ __attribute__((aligned(16))) u64 lds[NSEG * bmac_ld(LOGP)];  // 16-B pair accesses
     __shared__ __attribute__((aligned(16))) u64 ltw[NSEG * (2 * (1 << LOGP) + 2)];  // rows of 2P + 2 words: 16-B pairs
@@ -3037,7 +3122,25 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SI
     const int I = Imap[yi];
     const int kI = I == l ? K - 1 : I;
     const DevPrime pr = primes[kI];
-    if (yi < nint)
+    if constexpr (sizeof...(DRA) == 1) {
+        const BmacDR &d = (dra, ...);
+        BmacDRB db;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const u64 li = (u64)I << logN;
+            db.z[k] = d.Z + ((u64)((b * 2 + k) * l + I) << logN);
+            db.in[k] = (d.IN.p && k < d.in_nk) ? d.IN.p + b * d.IN.sb + k * d.IN.sk + li : nullptr;
+            db.out[k] = d.OUT.p + b * d.OUT.sb + k * d.OUT.sk + li;
+        }
+        db.w = d.inv[I];
+        db.wq = d.inv_q[I];
+        if (yi < nint)
+            bmac_body<LOGP, NSEG, EPT, false, SPL, true>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l, K,
+                                                         elt, db);
+        else
+            bmac_body<LOGP, NSEG, EPT, true, false, true>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l,
+                                                          K, elt, db);
+    } else if (yi < nint)
         bmac_body<LOGP, NSEG, EPT, false, SPL>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l, K, elt);
     else
         bmac_body<LOGP, NSEG, EPT, true>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l, K, elt);
@@ -3047,13 +3150,11 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SI
 // 200 VGPRs, 2 waves/SIMD) measured 1,062 vs 951 ms per step at cfg3 (round 3, gpurun_out/r03s)
 template <int LOGR, int LOGC, int NA, int NB2, int EPT = 4>
 static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l,
-                            int part, u32 elt)
+                            int part, u32 elt, const BmacDR *dr, int tsel)
 {
     constexpr int R = 1 << LOGR, C = 1 << LOGC;
     const TwTables fwd{c.tw, c.twb, c.twf, c.twbf, c.tws, c.twbs};
     // (2a) pass A of every mod-up NTT (B * l * l jobs), output E[b][I][J] (lazy, pass-A domain)
-    const int nint = c.imap_nint[l];
-    const int *dm = c.imap_at(l);
     if (part & 1) {
         ModUpMap m{l, c.logN, (int)c.K - 1};
         k_ntt<LOGR, NA, false, true, false><<<dim3(C / NA, B * l * l), NA * R / 16, 0, c.stream>>>(
@@ -3063,33 +3164,43 @@ static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *
         HEC_HIP(hipGetLastError());
         return;
     }
-    // (2b)+(3) fused; integer target primes first (slowest blocks start first)
+    // (2b)+(3) fused; integer target primes first (slowest blocks start first).  tsel 0: every target; 1: P alone;
+    // 2: the data targets with the divide-and-round epilogue (BmacDR)
     constexpr int TB = NB2 * C / EPT;
     constexpr int X = R / NB2;
-    const int gpad = (X * (l + 1) + 7) / 8 * 8;
-    if (c.bmac_split)
-        k_bmac<LOGC, NB2, EPT, true><<<dim3(gpad * B), TB, 0, c.stream>>>(T, E, key, ACC, fwd, c.primes, dm, l + 1,
-                                                                          c.logN, l, (int)c.K, nint, gpad, elt);
-    else
-        k_bmac<LOGC, NB2, EPT, false><<<dim3(gpad * B), TB, 0, c.stream>>>(T, E, key, ACC, fwd, c.primes, dm, l + 1,
-                                                                           c.logN, l, (int)c.K, nint, gpad, elt);
+    const int *dm = tsel == 0 ? c.imap_at(l) : c.imap_split_at(l) + (tsel == 2 ? 1 : 0);
+    const int nI = tsel == 0 ? l + 1 : tsel == 1 ? 1 : l;
+    const int nint = tsel == 0 ? c.imap_nint[l] : tsel == 1 ? c.imap_pint : c.imap_nint[l] - c.imap_pint;
+    const int gpad = (X * nI + 7) / 8 * 8;
+    auto launch = [&](auto spl) {
+        constexpr bool SPL = decltype(spl)::value;
+        if (tsel == 2)
+            k_bmac<LOGC, NB2, EPT, SPL, BmacDR><<<dim3(gpad * B), TB, 0, c.stream>>>(
+                T, E, key, ACC, fwd, c.primes, dm, nI, c.logN, l, (int)c.K, nint, gpad, elt, *dr);
+        else
+            k_bmac<LOGC, NB2, EPT, SPL><<<dim3(gpad * B), TB, 0, c.stream>>>(T, E, key, ACC, fwd, c.primes, dm, nI,
+                                                                            c.logN, l, (int)c.K, nint, gpad, elt);
+    };
+    if (c.bmac_split) launch(std::true_type{});
+    else launch(std::false_type{});
     HEC_HIP(hipGetLastError());
 }
 
 void ks_modup_mac(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l, int part,
-                  u32 elt)
+                  u32 elt, const BmacDR *dr, int tsel)
 {
+    if ((tsel == 2) != (dr != nullptr) || tsel < 0 || tsel > 2) throw std::logic_error("ks_modup_mac: target selection");
     // <LOGR, LOGC, pass-A columns per block, fused pass-B chunks per block>: k_bmac blocks of 64-128
     // threads (4 chunks at N = 2^15: 110 us per B = 8 call vs 128 / 166 us at 16 / 32 chunks) keep the
     // serial digit loop of the slow integer-prime blocks short
     switch (c.logN) {
-    case 10: run_modup_fused<5, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 11: run_modup_fused<6, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 12: run_modup_fused<6, 6, 64, 8>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 13: run_modup_fused<7, 6, 32, 8>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 14: run_modup_fused<7, 7, 32, 4>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 15: run_modup_fused<8, 7, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt); break;
-    case 16: run_modup_fused<8, 8, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt); break;
+    case 10: run_modup_fused<5, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 11: run_modup_fused<6, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 12: run_modup_fused<6, 6, 64, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 13: run_modup_fused<7, 6, 32, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 14: run_modup_fused<7, 7, 32, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 15: run_modup_fused<8, 7, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 16: run_modup_fused<8, 8, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
     default: throw std::invalid_argument("poly_modulus_degree must be 2^10 .. 2^16");
     }
 }
