@@ -161,6 +161,13 @@ def lib():
             "hec_bfft_diagonal": [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double),
                                   C.POINTER(C.c_double)],
             "hec_fft": [vp, vp, C.c_uint64, C.c_int, vp],
+            "hec_secret_key_upload": [vp, u64p, C.POINTER(vp)],
+            "hec_secret_key_download": [vp, u64p],
+            "hec_secret_key_destroy": [vp],
+            "hec_decrypt": [vp, vp, vp, C.c_uint64, vp],
+            "hec_decode": [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+            "hec_decrypt_decode": [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double)],
             "hec_bfft": [vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp],
         }
         for name, args in sig.items():
@@ -511,6 +518,51 @@ class Context:
         _check(lib().hec_encode_scalar(self.h, float(value), float(scale), level, pt.h))
         return pt
 
+    def secret_key(self, data):
+        """seal::SecretKey on the device (hec_secret_key_upload): data u64[K][N], NTT form at the key level"""
+        return SecretKey(self, data)
+
+    def _decoded(self, fn, handles, n_values, real):
+        nv = self.N // 2 if n_values is None else int(n_values)
+        re = np.zeros((len(handles), nv), dtype=np.float64)
+        im = None if real else np.zeros((len(handles), nv), dtype=np.float64)
+        arr = (C.c_void_p * max(1, len(handles)))(*handles)
+        dp = C.POINTER(C.c_double)
+        _check(fn(arr, len(handles), nv, re.ctypes.data_as(dp), im.ctypes.data_as(dp) if im is not None else None))
+        if real:
+            return re
+        out = np.empty(re.shape, dtype=np.complex128)
+        out.real, out.imag = re, im
+        return out
+
+    def decrypt(self, sk, cts):
+        """seal::Decryptor::decrypt for a batch (hec_decrypt; sizes and levels may differ): one NTT-form Plaintext
+        per ciphertext, with its level and scale (a single Plaintext for a single Ciphertext)."""
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        pts = [Plaintext(self, None, 1.0) for _ in cts]
+        _check(lib().hec_decrypt(self.h, sk.h, (C.c_void_p * max(1, len(cts)))(*[c.h.value for c in cts]), len(cts),
+                                 (C.c_void_p * max(1, len(pts)))(*[p.h.value for p in pts])))
+        return pts[0] if single else pts
+
+    def decode(self, pts, n_values=None, real=False):
+        """seal::CKKSEncoder::decode for a batch (hec_decode): the first n_values (default N/2) slots of every
+        plaintext as a complex128 array [count][n_values] (float64 with real=True, SEAL's vector<double> overload);
+        one row for a single Plaintext."""
+        single = isinstance(pts, Plaintext)
+        pts = [pts] if single else list(pts)
+        out = self._decoded(lambda *a: lib().hec_decode(self.h, *a), [p.h.value for p in pts], n_values, real)
+        return out[0] if single else out
+
+    def decrypt_decode(self, sk, cts, n_values=None, real=False):
+        """decrypt + decode in one pass with no Plaintext objects in between (hec_decrypt_decode): the doubles of
+        decode(decrypt(sk, cts))."""
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        out = self._decoded(lambda *a: lib().hec_decrypt_decode(self.h, sk.h, *a), [c.h.value for c in cts],
+                            n_values, real)
+        return out[0] if single else out
+
     def relin_key(self, data=None, seed=None):
         return KSwitchKey(self, data, seed)
 
@@ -826,6 +878,32 @@ class Plaintext:
         try:
             if self.h:
                 lib().hec_plaintext_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class SecretKey:
+    """seal::SecretKey on the device: u64[K][N], NTT form at the key level; wiped when destroyed."""
+
+    def __init__(self, ctx: Context, data):
+        self.ctx = ctx
+        a = np.ascontiguousarray(data, dtype=np.uint64)
+        if a.shape != (ctx.K, ctx.N):
+            raise InvalidArgument(HEC_EINVAL, "secret key is not valid for encryption parameters")
+        h = C.c_void_p()
+        _check(lib().hec_secret_key_upload(ctx.h, _p(a), C.byref(h)))
+        self.h = h
+
+    def download(self):
+        a = np.empty((self.ctx.K, self.ctx.N), dtype=np.uint64)
+        _check(lib().hec_secret_key_download(self.h, _p(a)))
+        return a
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().hec_secret_key_destroy(self.h)
                 self.h = None
         except Exception:
             pass

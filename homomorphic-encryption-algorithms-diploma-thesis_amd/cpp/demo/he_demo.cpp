@@ -1,8 +1,8 @@
 // he_demo — the reference's `demo matrix_operations batched_matmul_ckks` flow
 // (src/demos/matrix_operations.cpp:1042-1175) written against the hecdna drop-in headers:
 // identical he::operators / he::linalg code, with seal:: types replaced by hecdna:: types.
-// Key generation / encryption / decryption stay with the caller (SEAL in a real deployment); this
-// program reads SEAL-layout keys and ciphertexts from a file and writes the result ciphertexts.
+// Key generation and encryption stay with the caller (SEAL in a real deployment); this program reads SEAL-layout
+// keys and ciphertexts from a file and writes the result ciphertexts (mode decrypt: the decoded values).
 //
 // usage: he_demo <mode> <in.bin> <out.bin>
 //   mode = batched_diag   (COL_OR_DIAG = 1: A diag-batched x B col-batched)
@@ -23,6 +23,10 @@
 //                          the denominator, signed_inv(denom, 0.05, 6), the numerators, a and b)
 //          fft:<n>[:inv]  (he::fft::fft / ifft over the first <n> input ciphertexts, src/core/he_fft.cpp:70-87)
 //          bfft:<n>[:inv] (he::fft::bfft / ibfft of c0 with block size <n>, src/core/he_fft.cpp:208-223)
+//          decrypt        (the demos' last step, matrix_operations.cpp:1153-1156: Decryptor decr(ctx, sk);
+//                          decr.decrypt(ct, pt); cencd.decode(pt, values) for every input ciphertext.  The input file
+//                          carries the secret key after the Galois keys: u64 1, then u64[K][N]; the output is u64
+//                          count, u64 slot_count, then count rows of slot_count complex doubles (re, im))
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -53,6 +57,7 @@ struct Input {
     std::vector<Ct> cts;
     std::vector<std::uint64_t> rk;
     std::map<std::uint32_t, std::vector<std::uint64_t>> gk;
+    std::vector<std::uint64_t> sk;  // optional trailing section (mode decrypt)
 };
 
 template <class T>
@@ -99,6 +104,12 @@ Input read_input(const char *path)
         v.resize(kw);
         rd(f, v.data(), kw);
     }
+    std::uint64_t has_sk = 0;
+    f.read(reinterpret_cast<char *>(&has_sk), 8);  // absent in the inputs of every other mode
+    if (f && has_sk) {
+        in.sk.resize(K * in.N);
+        rd(f, in.sk.data(), in.sk.size());
+    }
     return in;
 }
 
@@ -123,7 +134,7 @@ int main(int argc, char **argv)
 {
     if (argc != 4) {
         std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|"
-                     "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|server> <in.bin> <out.bin>\n";
+                     "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|server> <in.bin> <out.bin>\n";
         return 1;
     }
     const std::string mode = argv[1];
@@ -342,6 +353,35 @@ int main(int argc, char **argv)
         Matrix B(2, 2, std::vector<Ciphertext>(cts.begin() + 4, cts.begin() + 8));
         Matrix C = A.matmul(eval, rk, B);
         for (const auto &c : C.get_elems()) keep.push_back(c);
+    } else if (mode == "decrypt") {
+        // matrix_operations.cpp:1060,1153-1156: Decryptor decr(ctx, secret_key); per result ciphertext
+        // decr.decrypt(ct, pt); cencd.decode(pt, values)
+        if (in.sk.empty()) throw std::runtime_error("decrypt: the input carries no secret key");
+        hecdna::SecretKey secret_key(ctx, in.sk.data());
+        hecdna::Decryptor decr(ctx, secret_key);
+        hecdna::CKKSEncoder cencd(ctx);
+        std::ofstream f(argv[3], std::ios::binary);
+        const std::uint64_t n = cts.size(), slots = ctx.slot_count();
+        f.write(reinterpret_cast<const char *>(&n), 8);
+        f.write(reinterpret_cast<const char *>(&slots), 8);
+        for (const Ciphertext &ct : cts) {
+            hecdna::Plaintext pt;
+            std::vector<std::complex<double>> values;
+            decr.decrypt(ct, pt);
+            cencd.decode(pt, values);
+            f.write(reinterpret_cast<const char *>(values.data()), values.size() * sizeof(values[0]));
+        }
+        if (!cts.empty()) {  // the first values, as the reference prints its result matrix
+            hecdna::Plaintext pt;
+            std::vector<double> values;
+            decr.decrypt(cts[0], pt);
+            cencd.decode(pt, values);
+            std::cout << "he_demo decrypt: c0 = [";
+            for (std::size_t i = 0; i < 4 && i < values.size(); ++i) std::cout << (i ? ", " : "") << values[i];
+            std::cout << ", ...]\n";
+        }
+        std::cout << "he_demo decrypt: wrote " << n << " x " << slots << " values\n";
+        return 0;
     } else if (mode == "encode") {
         // matrix_operations.cpp:1079-1087: mat1[c][r] = 2 + dim c + r; each column replicated over the
         // slots as BatchedVector does; CKKSEncoder cencd(ctx); cencd.encode(mat1[i], scale, pt[i])

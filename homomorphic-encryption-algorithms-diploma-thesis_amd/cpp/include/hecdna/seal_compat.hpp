@@ -12,6 +12,8 @@
 //                                                hec_encode_scalar; a parms_id or a level selects the level)
 //   seal::parms_id_type, get_context_data(...) -> hecdna::parms_id_type (BLAKE2b-256 of {scheme, N, the level's
 //      ->chain_index()                            moduli}, SEAL's parms_id), hecdna::ContextData
+//   seal::SecretKey / Decryptor::decrypt      -> hecdna::SecretKey / Decryptor (hec_decrypt)
+//   seal::CKKSEncoder::decode                 -> hecdna::CKKSEncoder::decode (on the GPU, hec_decode)
 //
 // Errors are rethrown with SEAL's exception types and messages (std::invalid_argument,
 // std::logic_error); HIP failures as std::runtime_error.  Objects live on the context's GPU.
@@ -426,6 +428,22 @@ public:
         encode_complex(std::vector<std::complex<double>>(slot_count(), value), ctx_->level_of(parms_id), scale,
                        destination);
     }
+    // CKKSEncoder::decode(plain, destination) (matrix_operations.cpp:127,1155): all slot_count() slots, the real
+    // parts for a vector<double> destination
+    void decode(const Plaintext &plain, std::vector<double> &destination) const
+    {
+        destination.assign(slot_count(), 0.0);
+        const hec_plaintext *p = plain.get();
+        check(hec_decode(ctx_->get(), &p, 1, slot_count(), destination.data(), nullptr));
+    }
+    void decode(const Plaintext &plain, std::vector<std::complex<double>> &destination) const
+    {
+        std::vector<double> re(slot_count()), im(slot_count());
+        const hec_plaintext *p = plain.get();
+        check(hec_decode(ctx_->get(), &p, 1, slot_count(), re.data(), im.data()));
+        destination.resize(slot_count());
+        for (std::size_t i = 0; i < re.size(); ++i) destination[i] = {re[i], im[i]};
+    }
     // every row must have the same length (at most slot_count())
     void encode_batch(const std::vector<std::vector<double>> &rows, double scale, std::vector<Plaintext> &destination) const
     {
@@ -454,6 +472,42 @@ private:
         check(hec_encode(ctx_->get(), re.data(), im.data(), values.size(), 1, scale, level, &p));
     }
     const Context *ctx_;
+};
+
+// seal::SecretKey (KeyGenerator::secret_key(), matrix_operations.cpp:1059-1060) on the device; wiped when the last
+// copy goes
+class SecretKey {
+public:
+    SecretKey() = default;
+    // SEAL layout u64[K][N], NTT form at the key level (SecretKey::data().data())
+    SecretKey(const Context &ctx, const std::uint64_t *data)
+    {
+        hec_secret_key *k = nullptr;
+        check(hec_secret_key_upload(ctx.get(), data, &k));
+        h_.reset(k, [](hec_secret_key *x) { hec_secret_key_destroy(x); });
+    }
+    hec_secret_key *get() const { return h_.get(); }
+
+private:
+    std::shared_ptr<hec_secret_key> h_;
+};
+
+// seal::Decryptor (reference: `Decryptor decr(ctx, secret_key); decr.decrypt(ct, pt)`,
+// src/demos/matrix_operations.cpp:1060,126,1154)
+class Decryptor {
+public:
+    Decryptor(const Context &ctx, const SecretKey &sk) : ctx_(&ctx), sk_(sk) {}
+    void decrypt(const Ciphertext &encrypted, Plaintext &destination) const
+    {
+        destination.bind(*ctx_);
+        const hec_ciphertext *c = encrypted.get();
+        hec_plaintext *p = destination.get();
+        check(hec_decrypt(ctx_->get(), sk_.get(), &c, 1, &p));
+    }
+
+private:
+    const Context *ctx_;
+    SecretKey sk_;
 };
 
 class RelinKeys {

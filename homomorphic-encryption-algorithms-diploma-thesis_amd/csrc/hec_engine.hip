@@ -105,6 +105,13 @@ struct hec_kswitch_key {
     u64 ctx_gen = 0;
     u64 *d = nullptr;
 };
+struct hec_secret_key {  // seal::SecretKey: u64[K][N], NTT form, key level
+    hec_context *ctx = nullptr;
+    u64 ctx_gen = 0;
+    int device = 0;  // for the wipe of a key that outlives its context
+    u64 *d = nullptr;
+    std::size_t words = 0;
+};
 struct hec_galois_keys {
     hec_context *ctx = nullptr;
     u64 ctx_gen = 0;
@@ -1719,6 +1726,8 @@ int hec_context_destroy(hec_context *ctx)
         for (double *p : {c.twf, c.itwf, c.twbf, c.itwbf}) (void)hipFree(p);
         (void)hipFree(c.enc_map);
         (void)hipFree(c.enc_tw);
+        (void)hipFree(c.dec_tw);
+        for (u64 *t : c.dec_crt) (void)hipFree(t);
         if (c.own_stream) (void)hipStreamDestroy(c.stream);
         for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
         delete ctx;
@@ -2196,6 +2205,291 @@ int hec_encode_scalar(hec_context *ctx, double value, double scale, uint64_t lev
         fill_limbs(c, out->d, (int)level, words);
         out->level = level;
         out->scale = scale;
+    });
+}
+
+// ------------------------------------------------------------------ decrypt / decode -------
+namespace {
+struct Big {  // a class member: no C language linkage inside the C-ABI block
+// little-endian multi-word x times a word
+static std::vector<u64> mul(const std::vector<u64> &x, u64 s)
+{
+    std::vector<u64> r(x.size() + 1, 0);
+    u64 carry = 0;
+    for (std::size_t i = 0; i < x.size(); ++i) {
+        const u128 t = (u128)x[i] * s + carry;
+        r[i] = (u64)t;
+        carry = (u64)(t >> 64);
+    }
+    r[x.size()] = carry;
+    while (r.size() > 1 && r.back() == 0) r.pop_back();
+    return r;
+}
+};
+// host tables of the GPU decoder (hec_decode.hip), built on first use: root_powers_[i] = ComplexRoots(2N).get_root(
+// bitrev(i, logN)) by the encoder's cos / sin route, and per level Q, (Q + 1) / 2, Q / q_i, (Q / q_i)^-1 mod q_i
+void decoder_tables(Ctx &c, std::size_t level)
+{
+    encoder_tables(c);  // the slot map
+    if (!c.dec_tw) {
+        const u64 N = c.N, m = 2 * N;
+        double (*volatile vcos)(double) = std::cos;
+        double (*volatile vsin)(double) = std::sin;
+        std::vector<std::complex<double>> roots(m / 8 + 1);
+        for (u64 i = 0; i <= m / 8; ++i) {
+            const double t = ((double)i * 6.283185307179586) / (double)m;
+            roots[i] = {vcos(t), vsin(t)};
+        }
+        std::vector<double> rp(2 * N, 0.0);
+        for (u64 i = 1; i < N; ++i) {
+            const auto r = SealRoots::get(m, roots, (u64)brev((u32)i, c.logN));
+            rp[2 * i] = r.real();
+            rp[2 * i + 1] = r.imag();
+        }
+        double *dt = nullptr;
+        HEC_HIP(hipMalloc(&dt, rp.size() * sizeof(double)));
+        HEC_HIP(hipMemcpyAsync(dt, rp.data(), rp.size() * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        c.dec_tw = dt;
+    }
+    if (c.dec_crt[level]) return;
+    std::vector<u64> Q{1};
+    for (std::size_t i = 0; i < level; ++i) Q = Big::mul(Q, c.q[i]);
+    const int wm = dec_wmax((int)Big::mul(Q, level).size());  // the composition's sum is below level Q
+    std::vector<u64> tab((2 + level) * wm + level, 0);
+    std::copy(Q.begin(), Q.end(), tab.begin());
+    {  // (Q + 1) / 2 = (Q >> 1) + 1 for odd Q
+        u64 *h = tab.data() + wm;
+        for (std::size_t j = 0; j < Q.size(); ++j) h[j] = (Q[j] >> 1) | (j + 1 < Q.size() ? Q[j + 1] << 63 : 0);
+        for (int j = 0; j < wm && ++h[j] == 0; ++j) {}
+    }
+    for (std::size_t i = 0; i < level; ++i) {
+        std::vector<u64> P{1};
+        u64 pm = 1;
+        for (std::size_t j = 0; j < level; ++j) {
+            if (j == i) continue;
+            P = Big::mul(P, c.q[j]);
+            pm = (u64)((u128)pm * (c.q[j] % c.q[i]) % c.q[i]);
+        }
+        std::copy(P.begin(), P.end(), tab.begin() + (2 + i) * wm);
+        tab[(2 + level) * wm + i] = level == 1 ? 1 : invm(pm, c.q[i]);
+    }
+    u64 *d = dalloc(tab.size());
+    HEC_HIP(hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+    HEC_HIP(hipStreamSynchronize(c.stream));
+    c.dec_crt[level] = d;
+    c.dec_wm[level] = wm;
+}
+
+struct DecEntry {
+    const u64 *d;
+    std::size_t size, level;  // size 1: a plaintext
+    double scale;
+};
+
+// The shared driver of hec_decrypt (pts != null), hec_decode (sk == null, size-1 entries) and hec_decrypt_decode:
+// rows in chunks that bound the work area, each chunk grouped by (size, level); every group runs k_decrypt, and,
+// when decoding, INTT -> CRT + upper layers -> LDS layers -> gather into the chunk's rows, copied out once per chunk.
+void dec_run(hec_context *ctx, const u64 *sk, const std::vector<DecEntry> &in, hec_plaintext *const *pts, u64 nv,
+             double *re, double *im)
+{
+    Ctx &c = ctx->c;
+    const u64 N = c.N, count = in.size();
+    const bool decode = pts == nullptr;
+    std::size_t lmax = 1;
+    for (const DecEntry &e : in) {
+        lmax = std::max(lmax, e.level);
+        if (decode) decoder_tables(c, e.level);
+    }
+    const u64 per = lmax * N + (decode ? 2 * N + 2 * nv : 0) + 4;
+    const u64 chunk = std::max<u64>(1, std::min<u64>({count, (u64(1) << 28) / per, 65535}));
+    std::vector<const u64 *> hsrc(chunk);
+    std::vector<double> his(chunk);
+    std::vector<u32> hrow(chunk);
+    for (u64 v0 = 0; v0 < count; v0 += chunk) {
+        const u64 cnt = std::min(chunk, count - v0);
+        Scratch s(c, cnt * per + 8 * 64);
+        u64 *X = s.take(cnt * lmax * N);
+        const u64 **dsrc = reinterpret_cast<const u64 **>(s.take(cnt));
+        double *dis = nullptr, *work = nullptr, *dre = nullptr, *dim = nullptr;
+        u32 *drow = nullptr;
+        if (decode) {
+            dis = reinterpret_cast<double *>(s.take(cnt));
+            drow = reinterpret_cast<u32 *>(s.take(cnt));
+            work = reinterpret_cast<double *>(s.take(cnt * 2 * N));
+            dre = reinterpret_cast<double *>(s.take(std::max<u64>(cnt * nv, 1)));
+            if (im) dim = reinterpret_cast<double *>(s.take(std::max<u64>(cnt * nv, 1)));
+        }
+        // the chunk's entries ordered by group; one upload of the pointer / scale / row lists for all groups
+        std::map<std::pair<std::size_t, std::size_t>, std::vector<u32>> groups;
+        for (u64 v = 0; v < cnt; ++v) groups[{in[v0 + v].size, in[v0 + v].level}].push_back((u32)v);
+        u64 k = 0;
+        for (const auto &g : groups)
+            for (u32 v : g.second) {
+                hsrc[k] = in[v0 + v].d;
+                his[k] = 1.0 / in[v0 + v].scale;
+                hrow[k] = v;
+                ++k;
+            }
+        HEC_HIP(hipMemcpyAsync(dsrc, hsrc.data(), cnt * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
+        if (decode) {
+            HEC_HIP(hipMemcpyAsync(dis, his.data(), cnt * sizeof(double), hipMemcpyHostToDevice, c.stream));
+            HEC_HIP(hipMemcpyAsync(drow, hrow.data(), cnt * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+        }
+        u64 b0 = 0, xoff = 0;
+        for (const auto &g : groups) {
+            const std::size_t size = g.first.first, level = g.first.second, n = g.second.size();
+            u64 *x = X + xoff;
+            {  // compulsory bytes: the ciphertexts and the key limbs read, the plaintexts written
+                ProfScope ps(c, "dec_decrypt", (double)(n * (size + 1) * level + (size > 1 ? level : 0)));
+                decrypt_batch(c, dsrc + b0, sk, (int)size, (int)level, (int)n, x);
+            }
+            if (decode) {
+                // the plaintext limbs read, N/2 complex slots written; 4 launches + the inverse NTT's two passes
+                ProfScope ps(c, "dec_decode", (double)(n * (level + 1)), 6);
+                decode_batch(c, x, (int)n, (int)level, c.dec_crt[level], c.dec_wm[level], dis + b0,
+                             work + b0 * 2 * N, nv, drow + b0, dre, dim);
+            } else {
+                for (std::size_t j = 0; j < n; ++j) {
+                    hec_plaintext *pt = pts[v0 + g.second[j]];
+                    const std::size_t w = level * N;
+                    if (pt->cap < w) {
+                        if (pt->d) HEC_HIP(hipFree(pt->d));
+                        pt->d = dalloc(w);
+                        pt->cap = w;
+                    }
+                    d2d(c, pt->d, x + j * w, w);
+                    pt->level = level;
+                    pt->scale = in[v0 + g.second[j]].scale;
+                }
+            }
+            b0 += n;
+            xoff += n * level * N;
+        }
+        if (decode && nv) {
+            HEC_HIP(hipMemcpyAsync(re + v0 * nv, dre, cnt * nv * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+            if (im)
+                HEC_HIP(hipMemcpyAsync(im + v0 * nv, dim, cnt * nv * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        }
+        HEC_HIP(hipStreamSynchronize(c.stream));  // host lists and outputs; the next chunk reuses the workspace
+    }
+}
+
+void check_sk(const hec_context *ctx, const hec_secret_key *sk)
+{
+    need(sk && sk->ctx == ctx && sk->ctx_gen == ctx->gen && sk->d, "secret key is not valid for encryption parameters");
+}
+void check_dec_scale(const Ctx &c, double scale, std::size_t level)
+{
+    if (!scale_ok(c, scale, level)) throw std::invalid_argument("scale out of bounds");
+}
+}  // namespace
+
+int hec_secret_key_upload(hec_context *ctx, const uint64_t *host, hec_secret_key **out)
+{
+    return guard([&] {
+        need(ctx && host && out, "null argument");
+        set_device(ctx);
+        Ctx &c = ctx->c;
+        auto *k = new hec_secret_key();
+        k->ctx = ctx;
+        k->ctx_gen = ctx->gen;
+        k->device = c.device;
+        k->words = c.K * c.N;
+        k->d = dalloc(k->words);
+        HEC_HIP(hipMemcpyAsync(k->d, host, k->words * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        *out = k;
+    });
+}
+int hec_secret_key_download(const hec_secret_key *sk, uint64_t *host)
+{
+    return guard([&] {
+        need(sk && host, "null argument");
+        need(ctx_alive(sk->ctx, sk->ctx_gen), "secret key is not valid for encryption parameters");
+        set_device(sk->ctx);
+        Ctx &c = sk->ctx->c;
+        HEC_HIP(hipMemcpyAsync(host, sk->d, sk->words * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+int hec_secret_key_destroy(hec_secret_key *sk)
+{
+    return guard([&] {
+        if (!sk) return;
+        // SEAL wipes a secret key's memory when it goes: zero-fill with the engine's fill kernel, on the context's
+        // stream while the context lives, else on the device's null stream (the key then touches nothing else)
+        (void)hipSetDevice(sk->device);
+        if (sk->d) {
+            const bool alive = ctx_alive(sk->ctx, sk->ctx_gen);
+            hipStream_t st = alive ? sk->ctx->c.stream : nullptr;
+            try {
+                Ctx wipe;
+                wipe.stream = st;
+                dev_fill32(wipe, sk->d, 0, sk->words * sizeof(u64));
+            } catch (...) {  // the memory is freed all the same
+            }
+            (void)hipStreamSynchronize(st);
+            (void)hipFree(sk->d);
+        }
+        delete sk;
+    });
+}
+
+int hec_decrypt(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
+                hec_plaintext *const *out)
+{
+    return guard([&] {
+        need(ctx && (count == 0 || (cts && out)), "null argument");
+        set_device(ctx);
+        check_sk(ctx, sk);
+        std::vector<DecEntry> in(count);
+        for (u64 i = 0; i < count; ++i) {
+            check_ct(ctx, cts[i]);
+            in[i] = {cts[i]->d, cts[i]->size, cts[i]->level, cts[i]->scale};
+        }
+        for (u64 i = 0; i < count; ++i)
+            need(out[i] && out[i]->ctx == ctx, "plain is not valid for encryption parameters");
+        if (count) dec_run(ctx, sk->d, in, out, 0, nullptr, nullptr);
+    });
+}
+
+int hec_decode(hec_context *ctx, const hec_plaintext *const *pts, uint64_t count, uint64_t n_values, double *re,
+               double *im)
+{
+    return guard([&] {
+        need(ctx && (count == 0 || pts) && (re || count * n_values == 0), "null argument");
+        set_device(ctx);
+        Ctx &c = ctx->c;
+        std::vector<DecEntry> in(count);
+        for (u64 i = 0; i < count; ++i) {
+            const hec_plaintext *p = pts[i];
+            need(p && p->ctx == ctx && p->d && p->level >= 1 && p->level <= c.L,
+                 "plain is not valid for encryption parameters");
+            in[i] = {p->d, 1, p->level, p->scale};
+        }
+        for (const DecEntry &e : in) check_dec_scale(c, e.scale, e.level);
+        if (n_values > c.N / 2) throw std::invalid_argument("values has invalid size");
+        if (count) dec_run(ctx, nullptr, in, nullptr, n_values, re, im);
+    });
+}
+
+int hec_decrypt_decode(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
+                       uint64_t n_values, double *re, double *im)
+{
+    return guard([&] {
+        need(ctx && (count == 0 || cts) && (re || count * n_values == 0), "null argument");
+        set_device(ctx);
+        Ctx &c = ctx->c;
+        check_sk(ctx, sk);
+        std::vector<DecEntry> in(count);
+        for (u64 i = 0; i < count; ++i) {
+            check_ct(ctx, cts[i]);
+            in[i] = {cts[i]->d, cts[i]->size, cts[i]->level, cts[i]->scale};
+        }
+        for (const DecEntry &e : in) check_dec_scale(c, e.scale, e.level);
+        if (n_values > c.N / 2) throw std::invalid_argument("values has invalid size");
+        if (count) dec_run(ctx, sk->d, in, nullptr, n_values, re, im);
     });
 }
 

@@ -101,6 +101,11 @@ struct Ctx {
     // inv_root_powers_ (complex[N], entry 0 unused)
     u32 *enc_map = nullptr;
     double *enc_tw = nullptr;
+    // CKKS decoder tables (hec_decode.hip), built on first decode: root_powers_ (complex[N], entry 0 unused) and per
+    // level the CRT table {Q, (Q + 1) / 2, Q / q_i ..., (Q / q_i)^-1 mod q_i ...} in dec_wm[level]-word numbers
+    double *dec_tw = nullptr;
+    u64 *dec_crt[HEC_MAXL + 1] = {};
+    int dec_wm[HEC_MAXL + 1] = {};
     Workspace ws;
     // host-side constants
     std::vector<u64> p_inv, p_inv_q, p_half_mod;            // key switch mod-down (per data prime)
@@ -260,6 +265,15 @@ void fill_limbs(Ctx &c, u64 *p, int nl, const u64 *words);
 // complex-scalar encode he::fft uses for its twiddles, period n its tiled diagonals)
 void encode_batch(Ctx &c, const double *re, const double *im, u64 nv, int count, double scale, int level, double *work,
                   u64 *out, u64 *maxabs, u64 period = 0);
+// Decryptor::decrypt and CKKSEncoder::decode (hec_decode.hip).  decrypt_batch: out[b][i] = sum_k src[b][k][i] s^k for
+// `count` entries of one size and level (src: device array of device pointers; size 1 copies).  decode_batch: x
+// [count][level][N] NTT form (transformed in place), crt / wmax the level's table and its word count (dec_wmax of the
+// words of level * Q), inv_scale[count] = 1 / scale per entry, work doubles [count][2N]; entry b's first nv slots go
+// to row row[b] of re / im (device doubles, nv per row; im may be null)
+int dec_wmax(int words);
+void decrypt_batch(Ctx &c, const u64 *const *src, const u64 *sk, int size, int level, int count, u64 *out);
+void decode_batch(Ctx &c, u64 *x, int count, int level, const u64 *crt, int wmax, const double *inv_scale,
+                  double *work, u64 nv, const u32 *row, double *re, double *im);
 // he::fft stage kernels (hec_kernels.hip, FftIOB): the last-limb products of nsrc source entries with their stage
 // plaintexts, their rounding limbs (divide_round's pass A), and the fused multiply-rescale-sum pass that writes
 // the stage's outputs at level l - 1

@@ -45,6 +45,7 @@ typedef struct hec_ciphertext hec_ciphertext;
 typedef struct hec_plaintext hec_plaintext;
 typedef struct hec_kswitch_key hec_kswitch_key; /* one KSwitchKeys entry: RelinKeys[0] */
 typedef struct hec_galois_keys hec_galois_keys; /* GaloisKeys: galois_elt -> key */
+typedef struct hec_secret_key hec_secret_key;   /* seal::SecretKey: u64[K][N], NTT form, key level */
 
 const char *hec_last_error(void);
 int hec_version(void);
@@ -131,6 +132,38 @@ int hec_encode(hec_context *ctx, const double *re, const double *im, uint64_t n_
  * "parms_id is not valid for encryption parameters", "scale out of bounds", "encoded value is too large" (also for a
  * non-finite value). */
 int hec_encode_scalar(hec_context *ctx, double value, double scale, uint64_t level, hec_plaintext *out);
+
+/* ---------------------------------------------------------------- client half: decrypt / decode */
+/* The last two calls of every reference demo (src/demos/matrix_operations.cpp:107,126-127,1153-1156; client.cpp,
+ * fft.cpp, math_operations.cpp): Decryptor::decrypt then CKKSEncoder::decode, for batches.  Decryption is bit-exact;
+ * the decoder follows SEAL 4.1's decode_internal (inverse NTT, exact CRT composition, centring on Q, the words summed
+ * into a double times 1 / scale, DWTHandler::transform_to_rev over root_powers_, slot i read at
+ * matrix_reps_index_map_[i]) as far as it can be restated without SEAL at hand: it is checked to a derived
+ * floating-point tolerance against this repository's CPU restatement, not to SEAL's bits.
+ * A batch may mix ciphertext sizes (>= 2) and levels (1 .. L); the engine groups it by (size, level).  Everything is
+ * ordered on the context's stream; calls with host outputs synchronise.  Nothing is written on an error. */
+/* seal::SecretKey (KeyGenerator::secret_key(), matrix_operations.cpp:1059-1060): host u64[K][N], NTT form at the key
+ * level.  Like every object it may be destroyed before or after its context; its device memory is zero-filled
+ * before it is freed, as SEAL wipes secret keys. */
+int hec_secret_key_upload(hec_context *ctx, const uint64_t *host, hec_secret_key **out);
+int hec_secret_key_download(const hec_secret_key *sk, uint64_t *host); /* u64[K][N], synchronises */
+int hec_secret_key_destroy(hec_secret_key *sk);
+/* Decryptor::decrypt (matrix_operations.cpp:126,1154; CKKS: dot_product_ct_sk_array): out[i] = sum_k cts[i][k] s^k
+ * per limb, NTT form; out[i] receives the ciphertext's level and scale.  Errors as SEAL: "encrypted is not valid for
+ * encryption parameters" (an empty handle, one of another context, size < 2), "secret key is not valid for
+ * encryption parameters", "plain is not valid for encryption parameters" (an output handle of another context). */
+int hec_decrypt(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
+                hec_plaintext *const *out);
+/* CKKSEncoder::decode (matrix_operations.cpp:127,1155) for `count` plaintexts: row v of re / im (host doubles,
+ * n_values each, n_values <= N/2) receives the first n_values slots; im == NULL keeps the real parts (SEAL's
+ * vector<double> overload).  Errors as SEAL: "plain is not valid for encryption parameters", "scale out of bounds"
+ * (scale <= 0 or int(log2 scale) >= the level's total coefficient-modulus bits, the encoder's rule), "values has
+ * invalid size" (n_values > N/2). */
+int hec_decode(hec_context *ctx, const hec_plaintext *const *pts, uint64_t count, uint64_t n_values, double *re,
+               double *im);
+/* both in one pass, with no plaintext objects in between; the doubles are those of hec_decode(hec_decrypt()) */
+int hec_decrypt_decode(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
+                       uint64_t n_values, double *re, double *im);
 
 /* ---------------------------------------------------------------- keys -------------------- */
 /* RelinKeys (KeyGenerator::create_relin_keys, matrix_operations.cpp:1061-1062): data u64[L][2][K][N] */
