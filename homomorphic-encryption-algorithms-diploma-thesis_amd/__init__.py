@@ -169,6 +169,17 @@ def lib():
             "hec_decrypt_decode": [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)],
             "hec_bfft": [vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp],
+            "hec_keygen_secret": [vp, u64p, C.POINTER(vp)],
+            "hec_keygen_public": [vp, vp, u64p, C.POINTER(vp)],
+            "hec_public_key_upload": [vp, u64p, C.POINTER(vp)],
+            "hec_public_key_download": [vp, u64p],
+            "hec_public_key_destroy": [vp],
+            "hec_keygen_relin": [vp, vp, u64p, C.POINTER(vp)],
+            "hec_keygen_galois": [vp, vp, C.POINTER(C.c_uint32), C.c_uint64, u64p],
+            "hec_encrypt_symmetric": [vp, vp, vp, C.c_uint64, u64p, vp, u64p],
+            "hec_encrypt": [vp, vp, vp, C.c_uint64, u64p, vp],
+            "hec_seal_ciphertext_save_seeded": [u64p, C.c_uint64, C.c_uint64, C.c_double, u64p, u64p, C.c_int, vp,
+                                                C.c_uint64, u64p],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -319,6 +330,28 @@ def seal_ciphertext_save(data: np.ndarray, scale: float, moduli, compr=COMPR_ZST
     m = np.ascontiguousarray(np.array(moduli, dtype=np.uint64))
     size, level, N = d.shape
     return _sized_out(lambda o, c, w: lib().hec_seal_ciphertext_save(_p(d), size, level, N, scale, _p(m), compr, o, c, w))
+
+
+def _seed_words(seed):
+    """A 64-byte prng_seed_type as 8 words (bytes, or 8 integers); None stays None (the library draws entropy)."""
+    if seed is None:
+        return None
+    a = (np.frombuffer(bytes(seed), dtype=np.uint64) if isinstance(seed, (bytes, bytearray))
+         else np.array(seed, dtype=np.uint64)).copy()
+    if a.shape != (8,):
+        raise InvalidArgument(HEC_EINVAL, "a seed is 64 bytes")
+    return a
+
+
+def seal_ciphertext_save_seeded(c0: np.ndarray, scale: float, moduli, prng_seed, compr=COMPR_ZSTD) -> bytes:
+    """Serializable<Ciphertext>::save of encrypt_symmetric(plain): c0 u64[level][N] and the seed of c1
+    (hec_seal_ciphertext_save_seeded; prng_seed = Context.encrypt_symmetric's public seed)."""
+    d = np.ascontiguousarray(c0, dtype=np.uint64)
+    m = np.ascontiguousarray(np.array(moduli, dtype=np.uint64))
+    sd = _seed_words(prng_seed)
+    level, N = d.shape
+    return _sized_out(lambda o, c, w: lib().hec_seal_ciphertext_save_seeded(_p(d), level, N, scale, _p(m), _p(sd),
+                                                                              compr, o, c, w))
 
 
 def seal_blake2xb(data: bytes, key: bytes, outlen: int) -> bytes:
@@ -521,6 +554,73 @@ class Context:
     def secret_key(self, data):
         """seal::SecretKey on the device (hec_secret_key_upload): data u64[K][N], NTT form at the key level"""
         return SecretKey(self, data)
+
+    # -------------------------------------------------------------- KeyGenerator / Encryptor
+    # seed: 64 bytes (or 8 words) that make the call's output a pure function of its arguments; None draws them
+    # from the operating system.  A seed must never be reused across calls.
+    @staticmethod
+    def _seed(seed):
+        a = _seed_words(seed)
+        return (None if a is None else _p(a)), a
+
+    def keygen_secret(self, seed=None):
+        """KeyGenerator::secret_key() on the GPU (hec_keygen_secret)"""
+        sp, _keep = self._seed(seed)
+        h = C.c_void_p()
+        _check(lib().hec_keygen_secret(self.h, sp, C.byref(h)))
+        return SecretKey(self, None, handle=h)
+
+    def keygen_public(self, sk, seed=None):
+        """KeyGenerator::create_public_key (hec_keygen_public)"""
+        sp, _keep = self._seed(seed)
+        h = C.c_void_p()
+        _check(lib().hec_keygen_public(self.h, sk.h, sp, C.byref(h)))
+        return PublicKey(self, None, handle=h)
+
+    def public_key(self, data):
+        """seal::PublicKey on the device (hec_public_key_upload): data u64[2][K][N]"""
+        return PublicKey(self, data)
+
+    def keygen_relin(self, sk, seed=None):
+        """KeyGenerator::create_relin_keys (hec_keygen_relin)"""
+        sp, _keep = self._seed(seed)
+        h = C.c_void_p()
+        _check(lib().hec_keygen_relin(self.h, sk.h, sp, C.byref(h)))
+        return KSwitchKey(self, handle=h)
+
+    def keygen_galois(self, sk, elts=None, seed=None, gk=None):
+        """KeyGenerator::create_galois_keys (hec_keygen_galois): the keys of `elts` (None: the default set) added to
+        gk (a new GaloisKeys when None)"""
+        sp, _keep = self._seed(seed)
+        gk = gk or GaloisKeys(self)
+        e = list(elts or [])
+        arr = (C.c_uint32 * max(1, len(e)))(*e)
+        _check(lib().hec_keygen_galois(gk.h, sk.h, arr, len(e), sp))
+        return gk
+
+    def encrypt_symmetric(self, sk, pts, seed=None, out=None, public_seeds=False):
+        """Encryptor::encrypt_symmetric for a batch (hec_encrypt_symmetric; levels may differ).  public_seeds=True
+        also returns u64[count][8], the seed of every c1 (for seal_ciphertext_save_seeded)."""
+        single = isinstance(pts, Plaintext)
+        pts = [pts] if single else list(pts)
+        out = ([out] if single and out is not None else out) or [Ciphertext(self) for _ in pts]
+        sp, _keep = self._seed(seed)
+        ps = np.zeros((len(pts), 8), dtype=np.uint64) if public_seeds else None
+        _check(lib().hec_encrypt_symmetric(self.h, sk.h, (C.c_void_p * max(1, len(pts)))(*[p.h.value for p in pts]),
+                                           len(pts), sp, self._arr(out) if out else None,
+                                           _p(ps) if ps is not None and ps.size else None))
+        res = out[0] if single else out
+        return (res, ps) if public_seeds else res
+
+    def encrypt(self, pk, pts, seed=None, out=None):
+        """Encryptor::encrypt with a public key for a batch (hec_encrypt)"""
+        single = isinstance(pts, Plaintext)
+        pts = [pts] if single else list(pts)
+        out = ([out] if single and out is not None else out) or [Ciphertext(self) for _ in pts]
+        sp, _keep = self._seed(seed)
+        _check(lib().hec_encrypt(self.h, pk.h, (C.c_void_p * max(1, len(pts)))(*[p.h.value for p in pts]), len(pts),
+                                 sp, self._arr(out) if out else None))
+        return out[0] if single else out
 
     def _decoded(self, fn, handles, n_values, real):
         nv = self.N // 2 if n_values is None else int(n_values)
@@ -886,8 +986,11 @@ class Plaintext:
 class SecretKey:
     """seal::SecretKey on the device: u64[K][N], NTT form at the key level; wiped when destroyed."""
 
-    def __init__(self, ctx: Context, data):
+    def __init__(self, ctx: Context, data, handle=None):
         self.ctx = ctx
+        if handle is not None:  # made on the device (Context.keygen_secret)
+            self.h = handle
+            return
         a = np.ascontiguousarray(data, dtype=np.uint64)
         if a.shape != (ctx.K, ctx.N):
             raise InvalidArgument(HEC_EINVAL, "secret key is not valid for encryption parameters")
@@ -909,11 +1012,43 @@ class SecretKey:
             pass
 
 
+class PublicKey:
+    """seal::PublicKey on the device: u64[2][K][N], NTT form at the key level."""
+
+    def __init__(self, ctx: Context, data, handle=None):
+        self.ctx = ctx
+        self.h = None
+        if handle is not None:  # made on the device (Context.keygen_public)
+            self.h = handle
+            return
+        a = np.ascontiguousarray(data, dtype=np.uint64)
+        if a.shape != (2, ctx.K, ctx.N):
+            raise InvalidArgument(HEC_EINVAL, "public key is not valid for encryption parameters")
+        h = C.c_void_p()
+        _check(lib().hec_public_key_upload(ctx.h, _p(a), C.byref(h)))
+        self.h = h
+
+    def download(self):
+        a = np.empty((2, self.ctx.K, self.ctx.N), dtype=np.uint64)
+        _check(lib().hec_public_key_download(self.h, _p(a)))
+        return a
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().hec_public_key_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 class KSwitchKey:
-    def __init__(self, ctx: Context, data=None, seed=None, seal_bytes: bytes | None = None):
+    def __init__(self, ctx: Context, data=None, seed=None, seal_bytes: bytes | None = None, handle=None):
         self.ctx = ctx
         h = C.c_void_p()
-        if seal_bytes is not None:  # RelinKeys::load(context, in, size)
+        if handle is not None:  # made on the device (Context.keygen_relin)
+            h = handle
+        elif seal_bytes is not None:  # RelinKeys::load(context, in, size)
             used = C.c_uint64()
             _check(lib().hec_kswitch_key_load_seal(ctx.h, C.c_char_p(seal_bytes), len(seal_bytes), C.byref(h),
                                                    C.byref(used)))

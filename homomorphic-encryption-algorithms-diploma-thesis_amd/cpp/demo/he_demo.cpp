@@ -1,8 +1,9 @@
 // he_demo — the reference's `demo matrix_operations batched_matmul_ckks` flow
 // (src/demos/matrix_operations.cpp:1042-1175) written against the hecdna drop-in headers:
 // identical he::operators / he::linalg code, with seal:: types replaced by hecdna:: types.
-// Key generation and encryption stay with the caller (SEAL in a real deployment); this program reads SEAL-layout
-// keys and ciphertexts from a file and writes the result ciphertexts (mode decrypt: the decoded values).
+// Most modes read SEAL-layout keys and ciphertexts from a file (made by the caller's own SEAL, or by this library) and
+// write the result ciphertexts (mode decrypt: the decoded values); mode selfcontained makes its own keys and
+// ciphertexts on the GPU from parameters, a seed and the clear data alone.
 //
 // usage: he_demo <mode> <in.bin> <out.bin>
 //   mode = batched_diag   (COL_OR_DIAG = 1: A diag-batched x B col-batched)
@@ -27,6 +28,14 @@
 //                          decr.decrypt(ct, pt); cencd.decode(pt, values) for every input ciphertext.  The input file
 //                          carries the secret key after the Galois keys: u64 1, then u64[K][N]; the output is u64
 //                          count, u64 slot_count, then count rows of slot_count complex doubles (re, im))
+//          selfcontained  (matrix_operations.cpp:1057-1156 with no other library: KeyGenerator, CKKSEncoder::encode,
+//                          Encryptor::encrypt, BatchedMatrix::matmul, Decryptor::decrypt, CKKSEncoder::decode.  The
+//                          input holds only parameters, a seed and the clear data: "HECSELF1", u64 N, u64 K, K bit
+//                          sizes (u64, for CoeffModulus::Create), f64 scale, u64 seeded (0: the operating system's
+//                          entropy), a 64-byte master seed (Blake2xbPRNGFactory(seed) handed to the parameters), u64
+//                          symmetric (0: Encryptor(ctx, pk).encrypt, the demo's; 1: Encryptor(ctx, sk)
+//                          .encrypt_symmetric), u64 COL_OR_DIAG, u64 dim, dim x dim doubles mat1[c][r].  The output is
+//                          that of mode decrypt)
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -128,13 +137,99 @@ void write_output(const char *path, const std::vector<const Ciphertext *> &cts)
         f.write(reinterpret_cast<const char *>(d.data()), d.size() * 8);
     }
 }
+
+// src/demos/matrix_operations.cpp:1042-1156 (bench_he_batched_matmul_ckks) over hecdna:: types, keys and ciphertexts
+// made here
+int selfcontained(const char *in_path, const char *out_path)
+{
+    std::ifstream f(in_path, std::ios::binary);
+    char magic[8];
+    rd(f, magic, 8);
+    if (std::memcmp(magic, "HECSELF1", 8)) throw std::runtime_error("bad magic");
+    std::uint64_t N, K, seeded, symmetric, col_or_diag, dim;
+    double scale;
+    hecdna::prng_seed_type seed;
+    rd(f, &N, 1);
+    rd(f, &K, 1);
+    if (K < 2 || K > 64) throw std::runtime_error("bad parameters");
+    std::vector<std::uint64_t> bits64(K);
+    rd(f, bits64.data(), K);
+    rd(f, &scale, 1);
+    rd(f, &seeded, 1);
+    rd(f, seed.data(), 8);
+    rd(f, &symmetric, 1);
+    rd(f, &col_or_diag, 1);
+    rd(f, &dim, 1);
+    if (dim == 0 || dim > N / 2) throw std::runtime_error("bad dimension");
+    std::vector<double> clear(dim * dim);
+    rd(f, clear.data(), clear.size());
+
+    hecdna::EncryptionParameters parms;
+    parms.set_poly_modulus_degree(N);
+    parms.set_coeff_modulus(hecdna::CoeffModulus::Create(N, std::vector<int>(bits64.begin(), bits64.end())));
+    if (seeded) parms.set_random_generator(std::make_shared<hecdna::Blake2xbPRNGFactory>(seed));
+    hecdna::Context ctx(parms);
+
+    hecdna::KeyGenerator kgen(ctx);
+    hecdna::SecretKey sk = kgen.secret_key();
+    hecdna::PublicKey pk;
+    kgen.create_public_key(pk);
+    hecdna::RelinKeys rk;
+    kgen.create_relin_keys(rk);
+    hecdna::GaloisKeys gk;
+    kgen.create_galois_keys(gk);
+    hecdna::Encryptor enc(ctx, pk);
+    enc.set_secret_key(sk);
+    hecdna::Decryptor dec(ctx, sk);
+    hecdna::CKKSEncoder cencd(ctx);
+    hecdna::Evaluator eval(ctx);
+
+    const std::size_t slot_no = cencd.slot_count();
+    std::vector<std::vector<std::complex<double>>> mat1(dim, std::vector<std::complex<double>>(slot_no));
+    for (std::size_t c = 0; c < dim; ++c)
+        for (std::size_t r = 0; r < slot_no; ++r) mat1[c][r] = std::complex<double>(clear[c * dim + r % dim], 0);
+    std::vector<hecdna::Plaintext> mat1_cols_pt(dim);
+    for (std::size_t i = 0; i < dim; ++i) cencd.encode(mat1[i], scale, mat1_cols_pt[i]);
+    std::vector<Ciphertext> mat1_cols_ct(dim);
+    for (std::size_t i = 0; i < dim; ++i) {
+        if (symmetric) enc.encrypt_symmetric(mat1_cols_pt[i], mat1_cols_ct[i]);
+        else enc.encrypt(mat1_cols_pt[i], mat1_cols_ct[i]);
+    }
+    std::vector<BatchedVector> mat1_cols_bvec;
+    mat1_cols_bvec.reserve(dim);
+    for (std::size_t i = 0; i < dim; ++i) mat1_cols_bvec.emplace_back(dim, std::move(mat1_cols_ct[i]));
+    std::vector<BatchedVector> res;
+    if (col_or_diag == 0) {
+        BatchedMatrix mat1_bmat(BatchedMatrix::BatchingType::col, std::move(mat1_cols_bvec));
+        BatchedMatrix mat2_bmat = mat1_bmat;
+        mat2_bmat.transp();
+        res = mat1_bmat.matmul(eval, rk, gk, mat2_bmat).get_bvecs();
+    } else {
+        BatchedMatrix mat1_bmat(BatchedMatrix::BatchingType::diag, mat1_cols_bvec);
+        BatchedMatrix mat2_bmat(BatchedMatrix::BatchingType::col, std::move(mat1_cols_bvec));
+        res = mat1_bmat.matmul(eval, rk, gk, mat2_bmat).get_bvecs();
+    }
+    std::ofstream o(out_path, std::ios::binary);
+    const std::uint64_t n = res.size(), slots = slot_no;
+    o.write(reinterpret_cast<const char *>(&n), 8);
+    o.write(reinterpret_cast<const char *>(&slots), 8);
+    hecdna::Plaintext mat3_diag_pt;
+    std::vector<std::complex<double>> values;
+    for (const auto &b : res) {
+        dec.decrypt(b.get_bvec(), mat3_diag_pt);
+        cencd.decode(mat3_diag_pt, values);
+        o.write(reinterpret_cast<const char *>(values.data()), values.size() * sizeof(values[0]));
+    }
+    std::cout << "he_demo selfcontained: wrote " << n << " x " << slots << " values\n";
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char **argv)
 {
     if (argc != 4) {
         std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|"
-                     "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|server> <in.bin> <out.bin>\n";
+                     "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|selfcontained|server> <in.bin> <out.bin>\n";
         return 1;
     }
     const std::string mode = argv[1];
@@ -165,6 +260,7 @@ int main(int argc, char **argv)
         std::cout << "he_demo server: read " << inet_buf_curpos << " bytes, wrote " << n << " bytes\n";
         return 0;
     }
+    if (mode == "selfcontained") return selfcontained(argv[2], argv[3]);
     const Input in = read_input(argv[2]);
 
     hecdna::Context ctx(in.N, in.moduli);  // SEALContext ctx(parms)

@@ -14,6 +14,9 @@
 //      ->chain_index()                            moduli}, SEAL's parms_id), hecdna::ContextData
 //   seal::SecretKey / Decryptor::decrypt      -> hecdna::SecretKey / Decryptor (hec_decrypt)
 //   seal::CKKSEncoder::decode                 -> hecdna::CKKSEncoder::decode (on the GPU, hec_decode)
+//   seal::KeyGenerator / PublicKey            -> hecdna::KeyGenerator / PublicKey (on the GPU, hec_keygen_*)
+//   seal::Encryptor, Serializable<Ciphertext> -> hecdna::Encryptor (hec_encrypt, hec_encrypt_symmetric), the seeded save
+//   seal::Blake2xbPRNGFactory(seed)           -> hecdna::Blake2xbPRNGFactory (EncryptionParameters::set_random_generator)
 //
 // Errors are rethrown with SEAL's exception types and messages (std::invalid_argument,
 // std::logic_error); HIP failures as std::runtime_error.  Objects live on the context's GPU.
@@ -63,12 +66,43 @@ inline void seal_check(int rc)
     if (rc != HEC_OK) throw std::logic_error(hec_seal_last_error());
 }
 
+// seal::prng_seed_type and seal::Blake2xbPRNGFactory(seed), SEAL's way to make a run deterministic:
+//   parms.set_random_generator(std::make_shared<Blake2xbPRNGFactory>(seed));
+// KeyGenerator and Encryptor take one fresh 64-byte seed per generating call from the context's factory: with a master
+// seed, call number k (counted over the factory's lifetime) uses BLAKE2Xb(input = u64 k, key = master seed, 64 bytes),
+// so no seed is ever used by two calls; without one (SEAL's default factory) every call draws its seed from the
+// operating system (getrandom) inside the library.
+using prng_seed_type = std::array<std::uint64_t, 8>;
+class UniformRandomGeneratorFactory {
+public:
+    UniformRandomGeneratorFactory() = default;
+    explicit UniformRandomGeneratorFactory(const prng_seed_type &seed) : seeded_(true), seed_(seed) {}
+    bool use_random_seed() const { return !seeded_; }
+    // the next call's seed into `out`; nullptr (the library draws entropy) for an unseeded factory
+    const std::uint64_t *next_seed(prng_seed_type &out)
+    {
+        if (!seeded_) return nullptr;
+        const std::uint64_t k = counter_++;
+        if (hec_seal_blake2xb(&k, 8, seed_.data(), 64, 64, out.data()) != HEC_OK)
+            throw std::logic_error(hec_seal_last_error());
+        return out.data();
+    }
+
+private:
+    bool seeded_ = false;
+    prng_seed_type seed_{};
+    std::uint64_t counter_ = 0;
+};
+using Blake2xbPRNGFactory = UniformRandomGeneratorFactory;
+
 // seal::EncryptionParameters (CKKS): the SEAL wire format load/save (server.cpp:110-112, client.cpp:82)
 class EncryptionParameters {
 public:
     EncryptionParameters() = default;
     EncryptionParameters(std::size_t poly_modulus_degree, std::vector<std::uint64_t> coeff_modulus)
         : n_(poly_modulus_degree), q_(std::move(coeff_modulus)) {}
+    void set_random_generator(std::shared_ptr<UniformRandomGeneratorFactory> rng) { rng_ = std::move(rng); }
+    const std::shared_ptr<UniformRandomGeneratorFactory> &random_generator() const { return rng_; }
     std::size_t poly_modulus_degree() const { return n_; }
     const std::vector<std::uint64_t> &coeff_modulus() const { return q_; }
     void set_poly_modulus_degree(std::size_t n) { n_ = n; }
@@ -95,6 +129,7 @@ public:
 private:
     std::size_t n_ = 0;
     std::vector<std::uint64_t> q_;
+    std::shared_ptr<UniformRandomGeneratorFactory> rng_;
 };
 
 // seal::parms_id_type: the BLAKE2b-256 hash of a level's EncryptionParameters (EncryptionParameters::compute_parms_id
@@ -139,7 +174,10 @@ class Context {
 public:
     // SEALContext ctx(parms) (server.cpp:112)
     explicit Context(const EncryptionParameters &parms, int device = 0)
-        : Context(parms.poly_modulus_degree(), parms.coeff_modulus(), device) {}
+        : Context(parms.poly_modulus_degree(), parms.coeff_modulus(), device)
+    {
+        if (parms.random_generator()) rng_ = parms.random_generator();
+    }
     Context(std::size_t poly_modulus_degree, const std::vector<std::uint64_t> &coeff_modulus, int device = 0)
     {
         hec_context *c = nullptr;
@@ -220,8 +258,11 @@ public:
     }
     bool has_comm() const { return hec_context_comm(h_.get(), nullptr, nullptr) == 1; }
     void synchronize() const { check(hec_context_synchronize(h_.get())); }
+    // the seed source of KeyGenerator and Encryptor (EncryptionParameters::set_random_generator; default: unseeded)
+    UniformRandomGeneratorFactory &random_generator() const { return *rng_; }
 
 private:
+    std::shared_ptr<UniformRandomGeneratorFactory> rng_ = std::make_shared<UniformRandomGeneratorFactory>();
     std::shared_ptr<hec_context> h_;
     std::vector<std::uint64_t> moduli_;
     std::vector<std::shared_ptr<const ContextData>> levels_;  // [level], index 0 unused
@@ -484,8 +525,10 @@ public:
     {
         hec_secret_key *k = nullptr;
         check(hec_secret_key_upload(ctx.get(), data, &k));
-        h_.reset(k, [](hec_secret_key *x) { hec_secret_key_destroy(x); });
+        adopt(k);
     }
+    // takes over a key made on the device (KeyGenerator)
+    void adopt(hec_secret_key *k) { h_.reset(k, [](hec_secret_key *x) { hec_secret_key_destroy(x); }); }
     hec_secret_key *get() const { return h_.get(); }
 
 private:
@@ -518,8 +561,10 @@ public:
     {
         hec_kswitch_key *k = nullptr;
         check(hec_kswitch_key_upload(ctx.get(), data, &k));
-        h_.reset(k, [](hec_kswitch_key *x) { hec_kswitch_key_destroy(x); });
+        adopt(k);
     }
+    // takes over a key made on the device (KeyGenerator::create_relin_keys)
+    void adopt(hec_kswitch_key *k) { h_.reset(k, [](hec_kswitch_key *x) { hec_kswitch_key_destroy(x); }); }
     hec_kswitch_key *get() const { return h_.get(); }
     // RelinKeys::load(context, in, size) (server.cpp:116)
     std::streamoff load(const Context &ctx, const seal_byte *in, std::size_t size)
@@ -558,6 +603,147 @@ public:
 
 private:
     std::shared_ptr<hec_galois_keys> h_;
+};
+
+// seal::PublicKey (KeyGenerator::create_public_key, matrix_operations.cpp:1059-1060) on the device
+class PublicKey {
+public:
+    PublicKey() = default;
+    // SEAL layout u64[2][K][N], NTT form at the key level (PublicKey::data().data())
+    PublicKey(const Context &ctx, const std::uint64_t *data)
+    {
+        hec_public_key *k = nullptr;
+        check(hec_public_key_upload(ctx.get(), data, &k));
+        adopt(k);
+    }
+    void adopt(hec_public_key *k) { h_.reset(k, [](hec_public_key *x) { hec_public_key_destroy(x); }); }
+    hec_public_key *get() const { return h_.get(); }
+
+private:
+    std::shared_ptr<hec_public_key> h_;
+};
+
+// seal::KeyGenerator (matrix_operations.cpp:1057-1064, client.cpp:87-90) on the GPU: the constructor makes the secret
+// key, every create_* call one more generating call with its own seed from the context's factory
+class KeyGenerator {
+public:
+    explicit KeyGenerator(const Context &ctx) : ctx_(&ctx)
+    {
+        prng_seed_type s;
+        hec_secret_key *k = nullptr;
+        check(hec_keygen_secret(ctx.get(), ctx.random_generator().next_seed(s), &k));
+        sk_.adopt(k);
+    }
+    KeyGenerator(const Context &ctx, const SecretKey &secret_key) : ctx_(&ctx), sk_(secret_key) {}
+    const SecretKey &secret_key() const { return sk_; }
+    void create_public_key(PublicKey &destination) const
+    {
+        prng_seed_type s;
+        hec_public_key *k = nullptr;
+        check(hec_keygen_public(ctx_->get(), sk_.get(), ctx_->random_generator().next_seed(s), &k));
+        destination.adopt(k);
+    }
+    void create_relin_keys(RelinKeys &destination) const
+    {
+        prng_seed_type s;
+        hec_kswitch_key *k = nullptr;
+        check(hec_keygen_relin(ctx_->get(), sk_.get(), ctx_->random_generator().next_seed(s), &k));
+        destination.adopt(k);
+    }
+    // the default set (GaloisTool::get_elts_all), a set of Galois elements, or the elements of rotation steps
+    void create_galois_keys(GaloisKeys &destination) const { create_galois_keys(std::vector<std::uint32_t>{}, destination); }
+    void create_galois_keys(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination) const
+    {
+        prng_seed_type s;
+        destination = GaloisKeys(*ctx_);
+        check(hec_keygen_galois(destination.get(), sk_.get(), galois_elts.data(), galois_elts.size(),
+                                ctx_->random_generator().next_seed(s)));
+    }
+    void create_galois_keys(const std::vector<int> &steps, GaloisKeys &destination) const
+    {
+        if (steps.empty()) throw std::invalid_argument("Galois element is not valid");  // not the default set
+        std::vector<std::uint32_t> elts;
+        for (int st : steps) elts.push_back(ctx_->galois_elt_from_step(st));
+        create_galois_keys(elts, destination);
+    }
+
+private:
+    const Context *ctx_;
+    SecretKey sk_;
+};
+
+// seal::Serializable<Ciphertext>, what Encryptor::encrypt_symmetric(plain) returns (client.cpp:113-114): its save
+// writes c0 and the seed of c1, about half the bytes of Ciphertext::save; the receiver's Ciphertext::load expands it
+template <class T>
+class Serializable;
+template <>
+class Serializable<Ciphertext> {
+public:
+    Serializable(Ciphertext ct, const prng_seed_type &c1_seed) : ct_(std::move(ct)), seed_(c1_seed) {}
+    std::streamoff save(std::ostream &out, compr_mode_type mode = compr_mode_type::zstd) const
+    {
+        const Context &ctx = ct_.context();
+        const std::vector<std::uint64_t> d = ct_.download();  // c0 is its first level * N words
+        std::uint64_t w = 0;
+        seal_check(hec_seal_ciphertext_save_seeded(d.data(), ct_.level(), ctx.poly_modulus_degree(), ct_.scale(),
+                                                   ctx.coeff_modulus().data(), seed_.data(), (int)mode, nullptr, 0, &w));
+        std::vector<char> b(w);
+        seal_check(hec_seal_ciphertext_save_seeded(d.data(), ct_.level(), ctx.poly_modulus_degree(), ct_.scale(),
+                                                   ctx.coeff_modulus().data(), seed_.data(), (int)mode, b.data(), w, &w));
+        out.write(b.data(), (std::streamsize)w);
+        return (std::streamoff)w;
+    }
+    const Ciphertext &object() const { return ct_; }  // the full ciphertext (no SEAL counterpart; for tests)
+
+private:
+    Ciphertext ct_;
+    prng_seed_type seed_;
+};
+
+// seal::Encryptor (matrix_operations.cpp:1065,1115; client.cpp:91,113-114) on the GPU
+class Encryptor {
+public:
+    Encryptor(const Context &ctx, const PublicKey &pk) : ctx_(&ctx), pk_(pk) {}
+    Encryptor(const Context &ctx, const SecretKey &sk) : ctx_(&ctx), sk_(sk) {}
+    Encryptor(const Context &ctx, const PublicKey &pk, const SecretKey &sk) : ctx_(&ctx), pk_(pk), sk_(sk) {}
+    void set_public_key(const PublicKey &pk) { pk_ = pk; }
+    void set_secret_key(const SecretKey &sk) { sk_ = sk; }
+    void encrypt(const Plaintext &plain, Ciphertext &destination) const
+    {
+        if (!pk_.get()) throw std::logic_error("public key is not set");
+        prng_seed_type s;
+        destination.bind(*ctx_);
+        const hec_plaintext *p = plain.get();
+        hec_ciphertext *c = destination.get();
+        check(hec_encrypt(ctx_->get(), pk_.get(), &p, 1, ctx_->random_generator().next_seed(s), &c));
+    }
+    void encrypt_symmetric(const Plaintext &plain, Ciphertext &destination) const
+    {
+        prng_seed_type c1_seed;
+        symmetric(plain, destination, c1_seed);
+    }
+    Serializable<Ciphertext> encrypt_symmetric(const Plaintext &plain) const
+    {
+        prng_seed_type c1_seed;
+        Ciphertext ct;
+        symmetric(plain, ct, c1_seed);
+        return Serializable<Ciphertext>(std::move(ct), c1_seed);
+    }
+
+private:
+    void symmetric(const Plaintext &plain, Ciphertext &destination, prng_seed_type &c1_seed) const
+    {
+        if (!sk_.get()) throw std::logic_error("secret key is not set");
+        prng_seed_type s;
+        destination.bind(*ctx_);
+        const hec_plaintext *p = plain.get();
+        hec_ciphertext *c = destination.get();
+        check(hec_encrypt_symmetric(ctx_->get(), sk_.get(), &p, 1, ctx_->random_generator().next_seed(s), &c,
+                                    c1_seed.data()));
+    }
+    const Context *ctx_;
+    PublicKey pk_;
+    SecretKey sk_;
 };
 
 // seal::Evaluator: const member functions, in-place and out-of-place forms

@@ -27,7 +27,9 @@
 #include <tuple>
 
 #include "hec_internal.h"
+#include "hec_keygen_host.h"
 
+#include <array>
 #include <dlfcn.h>
 #include <unistd.h>
 #include <rccl/rccl.h>
@@ -111,6 +113,11 @@ struct hec_secret_key {  // seal::SecretKey: u64[K][N], NTT form, key level
     int device = 0;  // for the wipe of a key that outlives its context
     u64 *d = nullptr;
     std::size_t words = 0;
+};
+struct hec_public_key {  // seal::PublicKey: u64[2][K][N], NTT form, key level
+    hec_context *ctx = nullptr;
+    u64 ctx_gen = 0;
+    u64 *d = nullptr;
 };
 struct hec_galois_keys {
     hec_context *ctx = nullptr;
@@ -1790,6 +1797,7 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "tensor_defer") c.tensor_defer_max = (int)std::max<int64_t>(1, value);
             else if (n == "tensor_bufs") c.tensor_defer_bufs = (int)std::max<int64_t>(1, value);
             else if (n == "tensor_xcd") c.tensor_xcd = (int)std::max<int64_t>(0, value);
+            else if (n == "prng_group") c.prng_group = in(0, 16);
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -2614,6 +2622,533 @@ int hec_galois_keys_destroy(hec_galois_keys *gk)
         for (auto &kv : gk->kw) (void)hipFree(kv.second);
         for (auto &kv : gk->mkey) (void)hipFree(kv.second);
         delete gk;
+    });
+}
+
+// ------------------------------------------------------------------ KeyGenerator / Encryptor
+// DESIGN.md 4.10.  Every call derives its sub-streams on the host (64-byte seeds), uploads them, and runs the
+// generator, the samplers, the noise NTTs and the fused RLWE kernel over all of its samples at once (in chunks that
+// bound the workspace).  The uniform sampler's redraws are resolved once per chunk: one read-back of the count, and
+// only when it is not zero the host walk over the streams' continuations and one scatter kernel.
+extern "C++" {  // helpers with templates and class return types inside the C-ABI block
+namespace {
+using Seed = std::array<u64, 8>;
+
+Seed master_seed(const uint64_t *seed)
+{
+    Seed m;
+    if (seed) std::memcpy(m.data(), seed, 64);
+    else if (!hec_host::entropy_seed(m.data())) throw std::logic_error("getrandom failed: no entropy for a seed");
+    return m;
+}
+Seed sub_seed(const Seed &m, u64 call, u64 role, u64 i, u64 j)
+{
+    Seed o;
+    hec_host::sub_seed(m.data(), call, role, i, j, o.data());
+    return o;
+}
+
+// host staging of a call's asynchronous uploads: kept until the call has drained the stream
+struct HostKeep {
+    std::vector<std::vector<u64>> bufs;
+};
+u64 *upload_words(Ctx &c, Scratch &s, HostKeep &keep, std::vector<u64> words)
+{
+    u64 *d = s.take(std::max<std::size_t>(words.size(), 1));
+    keep.bufs.push_back(std::move(words));
+    const std::vector<u64> &w = keep.bufs.back();
+    if (!w.empty()) HEC_HIP(hipMemcpyAsync(d, w.data(), w.size() * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+    return d;
+}
+u64 *upload_seeds(Ctx &c, Scratch &s, HostKeep &keep, const std::vector<Seed> &seeds)
+{
+    std::vector<u64> w(seeds.size() * 8);
+    for (std::size_t i = 0; i < seeds.size(); ++i) std::memcpy(&w[i * 8], seeds[i].data(), 64);
+    return upload_words(c, s, keep, std::move(w));
+}
+template <class T>
+T **upload_ptrs(Ctx &c, Scratch &s, HostKeep &keep, const std::vector<T *> &ptrs)
+{
+    static_assert(sizeof(T *) == sizeof(u64), "device pointers travel as words");
+    std::vector<u64> w(ptrs.size());
+    for (std::size_t i = 0; i < ptrs.size(); ++i) w[i] = (u64)(uintptr_t)ptrs[i];
+    return reinterpret_cast<T **>(upload_words(c, s, keep, std::move(w)));
+}
+u64 *fresh_words(Ctx &c, std::size_t words)  // an output buffer of a generating call
+{
+    u64 *d = dalloc(words);
+    if (c.poison) dev_fill(c, d, 0xFFFFFFFFu, words * sizeof(u64));
+    return d;
+}
+
+// SEAL's sample_poly_uniform for S streams at once: stream s draws nwords words, word g reduced mod q[g / N], into
+// dst[s].  The redrawn words come from the host walk (hec_host::redraw_walk) and one scatter launch.
+void sample_uniform(Ctx &c, Scratch &s, HostKeep &keep, const std::vector<Seed> &seeds, const std::vector<u64 *> &dst,
+                    u64 nwords, const u64 *q, int nl, const char *cls)
+{
+    const std::size_t S = seeds.size(), top = s.top;
+    if (!S) return;
+    UniSpec spec{};
+    for (int j = 0; j < nl; ++j) {
+        spec.q[j] = q[j];
+        spec.ratio[j] = (u64)((((u128)1) << 64) / q[j]);
+        spec.maxm[j] = ~0ull - ~0ull % q[j] - 1;
+    }
+    // a word is redrawn with probability < q / 2^64 <= 1/8 (q < 2^61): a quarter of the words and a floor for small
+    // calls is never reached
+    const u64 cap64 = std::min<u64>(S * nwords / 4 + 1024, 0x7fffffffu);
+    const u32 cap = (u32)cap64;
+    u64 *dseed = upload_seeds(c, s, keep, seeds);
+    u64 **ddst = upload_ptrs(c, s, keep, dst);
+    u64 *rej = s.take(cap), *val = nullptr;
+    u32 *cnt = reinterpret_cast<u32 *>(s.take(8));
+    dev_zero(c, cnt, 8);
+    {
+        ProfScope ps(c, cls, (double)S * (double)nwords / (double)c.N);  // the words written
+        prng_streams(c, dseed, ddst, (int)S, nwords, &spec, rej, cnt, cap);
+    }
+    u32 n = 0;
+    HEC_HIP(hipMemcpyAsync(&n, cnt, sizeof(u32), hipMemcpyDeviceToHost, c.stream));
+    HEC_HIP(hipStreamSynchronize(c.stream));
+    if (n) {
+        if (n > cap) throw std::logic_error("uniform sampler: redraw list overflow");
+        std::vector<u64> pos(n), v(n);
+        HEC_HIP(hipMemcpyAsync(pos.data(), rej, n * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        std::sort(pos.begin(), pos.end());  // (stream, position): the order the host routine meets them
+        std::vector<u64> g;
+        for (std::size_t a = 0; a < n;) {
+            std::size_t b = a;
+            const u64 st = pos[a] >> 32;
+            g.clear();
+            for (; b < n && pos[b] >> 32 == st; ++b) g.push_back(pos[b] & 0xffffffffull);
+            hec_host::redraw_walk(seeds[st].data(), nwords, c.N, q, g.data(), g.size(), v.data() + a);
+            a = b;
+        }
+        u64 *dpos = upload_words(c, s, keep, std::move(pos));
+        val = upload_words(c, s, keep, std::move(v));
+        ProfScope ps(c, "k:k_sample/redraw", 0);
+        scatter_words(c, ddst, dpos, val, (int)n);
+    }
+    s.top = top;
+}
+std::size_t uniform_words(std::size_t S, u64 nwords) { return S * (nwords / 4 + 16) + 2 * (S * nwords / 4 + 1024) + 16 * 64; }
+
+// `e` of S streams: the raw stream bytes, the centred binomial, its residues on nl primes, the forward NTTs:
+// E[s][j][i], NTT form
+void sample_noise(Ctx &c, Scratch &s, HostKeep &keep, const std::vector<Seed> &seeds, u64 *E, int nl)
+{
+    const std::size_t S = seeds.size(), top = s.top;
+    if (!S) return;
+    const u64 N = c.N, nwords = 6 * N / 8, stride = (nwords + 63) & ~(u64)63;
+    u64 *raw = s.take(S * stride);
+    std::vector<u64 *> dst(S);
+    for (std::size_t i = 0; i < S; ++i) dst[i] = raw + i * stride;
+    u64 *dseed = upload_seeds(c, s, keep, seeds);
+    u64 **ddst = upload_ptrs(c, s, keep, dst);
+    {
+        ProfScope ps(c, "k:k_prng/raw", (double)S * 0.75);
+        prng_streams(c, dseed, ddst, (int)S, nwords, nullptr, nullptr, nullptr, 0);
+    }
+    {
+        ProfScope ps(c, "k:k_sample/cbd", (double)S * (0.75 + nl));
+        sample_cbd(c, raw, stride, E, (int)S, nl);
+    }
+    int pm[HEC_MAXL + 1];
+    for (int j = 0; j < nl; ++j) pm[j] = j;
+    ProfScope ps(c, "k:k_ntt/keygen", 4.0 * S * nl, 2);
+    ntt_strided(c, false, E, nl * N, E, nl * N, nl, pm, (int)(S * nl));
+    s.top = top;
+}
+std::size_t noise_words(const Ctx &c, std::size_t S) { return S * (c.N + 64 + 16) + 8 * 64; }
+
+// a ternary polynomial per stream: the uniform sampler with the modulus 3 over N words, coefficient (v mod 3) - 1,
+// its residues on nl primes, NTT form: out[s][j][i].  wipe: the coefficient words are zeroed (a secret key's)
+void sample_ternary(Ctx &c, Scratch &s, HostKeep &keep, const std::vector<Seed> &seeds, u64 *out, int nl, bool wipe)
+{
+    const std::size_t S = seeds.size(), top = s.top;
+    if (!S) return;
+    const u64 N = c.N, three = 3;
+    u64 *T = s.take(S * N);
+    std::vector<u64 *> dst(S);
+    for (std::size_t i = 0; i < S; ++i) dst[i] = T + i * N;
+    sample_uniform(c, s, keep, seeds, dst, N, &three, 1, "k:k_prng/ternary");
+    {
+        ProfScope ps(c, "k:k_sample/ternary", (double)S * (1 + nl));
+        ternary_expand(c, T, out, (int)S, nl);
+    }
+    if (wipe) dev_zero(c, T, S * N * sizeof(u64));
+    int pm[HEC_MAXL + 1];
+    for (int j = 0; j < nl; ++j) pm[j] = j;
+    ProfScope ps(c, "k:k_ntt/keygen", 4.0 * S * nl, 2);
+    ntt_strided(c, false, out, nl * N, out, nl * N, nl, pm, (int)(S * nl));
+    s.top = top;
+}
+std::size_t ternary_words(const Ctx &c, std::size_t S) { return S * (c.N + 64) + uniform_words(S, c.N); }
+
+// encrypt_zero_symmetric for a batch over the primes 0 .. nl - 1: c1 = a, c0 = -(a s + NTT(e)) (+ the job's term)
+struct RlweReq {
+    u64 *c0, *c1;
+    const u64 *add;
+    u64 add_mul;
+    int add_limb;
+    Seed a, e;
+};
+std::size_t rlwe_words(const Ctx &c, std::size_t B, std::size_t nl)
+{
+    return B * (nl * c.N + 64 + sizeof(RlweJob) / 8 + 8) + uniform_words(B, nl * c.N) + noise_words(c, B) + 8 * 64;
+}
+std::size_t rlwe_chunk(const Ctx &c, std::size_t count, std::size_t nl)  // samples per pass: about 1 GiB of workspace
+{
+    return std::max<std::size_t>(1, std::min<std::size_t>({count, (std::size_t(1) << 27) / rlwe_words(c, 1, nl), 32767}));
+}
+void rlwe_batch(Ctx &c, Scratch &s, HostKeep &keep, const u64 *sk, int nl, const RlweReq *req, std::size_t B)
+{
+    const std::size_t top = s.top;
+    const u64 N = c.N;
+    std::vector<Seed> sa(B), se(B);
+    std::vector<u64 *> dst(B);
+    std::vector<u64> jobs(B * (sizeof(RlweJob) / 8));
+    double add_limbs = 0;
+    for (std::size_t b = 0; b < B; ++b) {
+        sa[b] = req[b].a;
+        se[b] = req[b].e;
+        dst[b] = req[b].c1;
+        const RlweJob j{req[b].c0, req[b].c1, req[b].add, req[b].add_mul, req[b].add_limb, 0};
+        std::memcpy(&jobs[b * (sizeof(RlweJob) / 8)], &j, sizeof(RlweJob));
+        add_limbs += !req[b].add ? 0 : req[b].add_limb < 0 ? nl : 1;
+    }
+    u64 *E = s.take(B * nl * N);
+    sample_uniform(c, s, keep, sa, dst, (u64)nl * N, c.q.data(), nl, "k:k_prng/uniform");
+    sample_noise(c, s, keep, se, E, nl);
+    const RlweJob *djobs = reinterpret_cast<const RlweJob *>(upload_words(c, s, keep, std::move(jobs)));
+    {
+        ProfScope ps(c, "k:k_rlwe/sym", 4.0 * B * nl + add_limbs);  // a, s, e read, c0 written, the added term read
+        rlwe_c0(c, djobs, sk, E, (int)B, nl);
+    }
+    s.top = top;
+}
+
+void check_pk(const hec_context *ctx, const hec_public_key *pk)
+{
+    need(pk && pk->ctx == ctx && pk->ctx_gen == ctx->gen && pk->d, "public key is not valid for encryption parameters");
+}
+void check_plain(const hec_context *ctx, const hec_plaintext *p)
+{
+    need(p && p->ctx == ctx && p->d && p->level >= 1 && p->level <= ctx->c.L,
+         "plain is not valid for encryption parameters");
+}
+static_assert(sizeof(RlweJob) % 8 == 0, "RlweJob is uploaded as words");
+
+// generate_one_kswitch_key for nkeys keys at once: key t's digit J is an RLWE sample over all K primes with
+// (P mod q_J) newkey_t[J] added to limb J of c0; seeds sub(call, role, J, tag_t)
+void kswitch_keygen(Ctx &c, const u64 *sk, const Seed &m, u64 call, u64 *const *keys, const u64 *const *newkey,
+                    const u64 *tags, std::size_t nkeys, Scratch &s, HostKeep &keep)
+{
+    const u64 N = c.N, K = c.K, L = c.L, P = c.q[K - 1];
+    std::vector<RlweReq> req;
+    for (std::size_t t = 0; t < nkeys; ++t)
+        for (u64 J = 0; J < L; ++J) {
+            u64 *d = keys[t] + J * 2 * K * N;
+            req.push_back({d, d + K * N, newkey[t], P % c.q[J], (int)J, sub_seed(m, call, 1, J, tags[t]),
+                           sub_seed(m, call, 2, J, tags[t])});
+        }
+    const std::size_t chunk = rlwe_chunk(c, req.size(), K);
+    for (std::size_t b0 = 0; b0 < req.size(); b0 += chunk)
+        rlwe_batch(c, s, keep, sk, (int)K, req.data() + b0, std::min(chunk, req.size() - b0));
+}
+}  // namespace
+}  // extern "C++"
+
+int hec_keygen_secret(hec_context *ctx, const uint64_t seed[8], hec_secret_key **out)
+{
+    return guard([&] {
+        need(ctx && out, "null argument");
+        set_device(ctx);
+        Ctx &c = ctx->c;
+        const Seed m = master_seed(seed);
+        auto *k = new hec_secret_key();
+        k->ctx = ctx;
+        k->ctx_gen = ctx->gen;
+        k->device = c.device;
+        k->words = c.K * c.N;
+        try {
+            k->d = fresh_words(c, k->words);
+            HostKeep keep;
+            Scratch s(c, ternary_words(c, 1));
+            sample_ternary(c, s, keep, {sub_seed(m, 1, 3, 0, 0)}, k->d, (int)c.K, true);
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        } catch (...) {
+            (void)hec_secret_key_destroy(k);
+            throw;
+        }
+        *out = k;
+    });
+}
+
+int hec_keygen_public(hec_context *ctx, const hec_secret_key *sk, const uint64_t seed[8], hec_public_key **out)
+{
+    return guard([&] {
+        need(ctx && out, "null argument");
+        set_device(ctx);
+        check_sk(ctx, sk);
+        Ctx &c = ctx->c;
+        const Seed m = master_seed(seed);
+        auto *k = new hec_public_key();
+        k->ctx = ctx;
+        k->ctx_gen = ctx->gen;
+        try {
+            k->d = fresh_words(c, 2 * c.K * c.N);
+            HostKeep keep;
+            Scratch s(c, rlwe_words(c, 1, c.K));
+            const RlweReq r{k->d, k->d + c.K * c.N, nullptr, 0, -1, sub_seed(m, 2, 1, 0, 0), sub_seed(m, 2, 2, 0, 0)};
+            rlwe_batch(c, s, keep, sk->d, (int)c.K, &r, 1);
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        } catch (...) {
+            (void)hec_public_key_destroy(k);
+            throw;
+        }
+        *out = k;
+    });
+}
+
+int hec_public_key_upload(hec_context *ctx, const uint64_t *host, hec_public_key **out)
+{
+    return guard([&] {
+        need(ctx && host && out, "null argument");
+        set_device(ctx);
+        Ctx &c = ctx->c;
+        auto *k = new hec_public_key();
+        k->ctx = ctx;
+        k->ctx_gen = ctx->gen;
+        try {
+            k->d = dalloc(2 * c.K * c.N);
+            HEC_HIP(hipMemcpyAsync(k->d, host, 2 * c.K * c.N * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        } catch (...) {
+            (void)hec_public_key_destroy(k);
+            throw;
+        }
+        *out = k;
+    });
+}
+int hec_public_key_download(const hec_public_key *pk, uint64_t *host)
+{
+    return guard([&] {
+        need(pk && host, "null argument");
+        need(ctx_alive(pk->ctx, pk->ctx_gen), "public key is not valid for encryption parameters");
+        set_device(pk->ctx);
+        Ctx &c = pk->ctx->c;
+        HEC_HIP(hipMemcpyAsync(host, pk->d, 2 * c.K * c.N * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+int hec_public_key_destroy(hec_public_key *pk)
+{
+    return guard([&] {
+        if (!pk) return;
+        if (ctx_alive(pk->ctx, pk->ctx_gen)) (void)hipStreamSynchronize(pk->ctx->c.stream);
+        (void)hipFree(pk->d);
+        delete pk;
+    });
+}
+
+int hec_keygen_relin(hec_context *ctx, const hec_secret_key *sk, const uint64_t seed[8], hec_kswitch_key **out)
+{
+    return guard([&] {
+        need(ctx && out, "null argument");
+        set_device(ctx);
+        check_sk(ctx, sk);
+        Ctx &c = ctx->c;
+        const Seed m = master_seed(seed);
+        auto *k = new hec_kswitch_key();
+        k->ctx = ctx;
+        k->ctx_gen = ctx->gen;
+        try {
+            k->d = fresh_words(c, key_words(c));
+            HostKeep keep;
+            const std::size_t B = rlwe_chunk(c, c.L, c.K);
+            Scratch s(c, c.K * c.N + 64 + rlwe_words(c, B, c.K));
+            u64 *S2 = s.take(c.K * c.N);  // newkey = s (*) s
+            {
+                ProfScope ps(c, "k:k_dyadic", 3.0 * c.K);
+                ew_dyadic(c, sk->d, sk->d, S2, 0, (int)c.K, 1);
+            }
+            const u64 *nk = S2;
+            const u64 tag = 0;
+            kswitch_keygen(c, sk->d, m, 3, &k->d, &nk, &tag, 1, s, keep);
+            dev_zero(c, S2, c.K * c.N * sizeof(u64));  // a function of the secret key
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        } catch (...) {
+            (void)hec_kswitch_key_destroy(k);
+            throw;
+        }
+        *out = k;
+    });
+}
+
+int hec_keygen_galois(hec_galois_keys *gk, const hec_secret_key *sk, const uint32_t *elts, uint64_t n,
+                      const uint64_t seed[8])
+{
+    return guard([&] {
+        need(gk && (elts || n == 0), "null argument");
+        need(ctx_alive(gk->ctx, gk->ctx_gen), "null argument");
+        hec_context *ctx = gk->ctx;
+        set_device(ctx);
+        check_sk(ctx, sk);
+        Ctx &c = ctx->c;
+        std::vector<u32> es(elts, elts + n);
+        if (n == 0) {
+            es.resize(hec_default_galois_elts(ctx, nullptr));
+            (void)hec_default_galois_elts(ctx, es.data());
+        }
+        for (u32 e : es) gk_check_elt(c, e);
+        std::sort(es.begin(), es.end());
+        es.erase(std::unique(es.begin(), es.end()), es.end());
+        const Seed m = master_seed(seed);
+        HEC_HIP(hipStreamSynchronize(c.stream));  // a replaced key may still be read by enqueued work
+        const u64 N = c.N, K = c.K;
+        // keys per pass: their permuted secret keys and their L digits each within the workspace bound
+        const std::size_t per_key = K * N + 64 + rlwe_words(c, c.L, K);
+        const std::size_t kc = std::max<std::size_t>(1, std::min<std::size_t>(es.size(), (std::size_t(1) << 27) / per_key));
+        for (std::size_t e0 = 0; e0 < es.size(); e0 += kc) {
+            const std::size_t cnt = std::min(kc, es.size() - e0);
+            HostKeep keep;
+            Scratch s(c, cnt * per_key + 64);
+            u64 *G = s.take(cnt * K * N);
+            std::vector<u64 *> keys(cnt);
+            std::vector<const u64 *> nk(cnt);
+            std::vector<u64> tags(cnt);
+            for (std::size_t t = 0; t < cnt; ++t) {
+                const u32 e = es[e0 + t];
+                u64 *&d = gk->keys[e];
+                if (!d) d = fresh_words(c, key_words(c));
+                gk->drop_kw(e);
+                keys[t] = d;
+                nk[t] = G + t * K * N;
+                tags[t] = e;
+                ProfScope ps(c, "galois");
+                galois_permute(c, PolyArr{sk->d, 0, 0}, PolyArr{G + t * K * N, 0, 0}, 1, 1, (int)K, e);
+            }
+            kswitch_keygen(c, sk->d, m, 4, keys.data(), nk.data(), tags.data(), cnt, s, keep);
+            dev_zero(c, G, cnt * K * N * sizeof(u64));  // permutations of the secret key
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        }
+    });
+}
+
+int hec_encrypt_symmetric(hec_context *ctx, const hec_secret_key *sk, const hec_plaintext *const *pts, uint64_t count,
+                          const uint64_t seed[8], hec_ciphertext *const *out, uint64_t *public_seeds)
+{
+    return guard([&] {
+        need(ctx && (count == 0 || (pts && out)), "null argument");
+        set_device(ctx);
+        check_sk(ctx, sk);
+        Ctx &c = ctx->c;
+        for (u64 v = 0; v < count; ++v) check_plain(ctx, pts[v]);
+        for (u64 v = 0; v < count; ++v)
+            need(out[v] && out[v]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        const Seed m = master_seed(seed);
+        const u64 N = c.N;
+        std::map<std::size_t, std::vector<u64>> groups;  // by level, as hec_decrypt groups
+        for (u64 v = 0; v < count; ++v) groups[pts[v]->level].push_back(v);
+        for (const auto &g : groups) {
+            const std::size_t l = g.first, chunk = rlwe_chunk(c, g.second.size(), l);
+            for (std::size_t b0 = 0; b0 < g.second.size(); b0 += chunk) {
+                const std::size_t B = std::min(chunk, g.second.size() - b0);
+                HostKeep keep;
+                Scratch s(c, rlwe_words(c, B, l));
+                std::vector<RlweReq> req(B);
+                for (std::size_t b = 0; b < B; ++b) {
+                    const u64 v = g.second[b0 + b];
+                    hec_ciphertext *ct = out[v];
+                    ensure(ct, 2 * l * N);
+                    req[b] = {ct->d, ct->d + l * N, pts[v]->d, 0, -1, sub_seed(m, 5, 1, v, 0), sub_seed(m, 5, 2, v, 0)};
+                    if (public_seeds) std::memcpy(public_seeds + v * 8, req[b].a.data(), 64);
+                }
+                rlwe_batch(c, s, keep, sk->d, (int)l, req.data(), B);
+                for (std::size_t b = 0; b < B; ++b) {
+                    hec_ciphertext *ct = out[g.second[b0 + b]];
+                    ct->size = 2;
+                    ct->level = l;
+                    ct->scale = pts[g.second[b0 + b]]->scale;
+                }
+                HEC_HIP(hipStreamSynchronize(c.stream));
+            }
+        }
+    });
+}
+
+int hec_encrypt(hec_context *ctx, const hec_public_key *pk, const hec_plaintext *const *pts, uint64_t count,
+                const uint64_t seed[8], hec_ciphertext *const *out)
+{
+    return guard([&] {
+        need(ctx && (count == 0 || (pts && out)), "null argument");
+        set_device(ctx);
+        check_pk(ctx, pk);
+        Ctx &c = ctx->c;
+        for (u64 v = 0; v < count; ++v) check_plain(ctx, pts[v]);
+        for (u64 v = 0; v < count; ++v)
+            need(out[v] && out[v]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        const Seed m = master_seed(seed);
+        const u64 N = c.N, K = c.K;
+        std::map<std::size_t, std::vector<u64>> groups;
+        for (u64 v = 0; v < count; ++v) groups[pts[v]->level].push_back(v);
+        for (const auto &g : groups) {
+            const std::size_t l = g.first, nl = l + 1;  // the level above: primes 0 .. l (l = L: prime l is P)
+            const std::size_t per = N * (nl + 2 * nl + 2 + 4 * l) + 8 * 64 + ternary_words(c, 1) + noise_words(c, 2);
+            const std::size_t chunk = std::max<std::size_t>(
+                1, std::min<std::size_t>({g.second.size(), (std::size_t(1) << 27) / per, 16383}));
+            const std::vector<u64> &inv = l < c.L ? c.ql_inv[l + 1] : c.p_inv;
+            const std::vector<u64> &inv_q = l < c.L ? c.ql_inv_q[l + 1] : c.p_inv_q;
+            for (std::size_t b0 = 0; b0 < g.second.size(); b0 += chunk) {
+                const std::size_t B = std::min(chunk, g.second.size() - b0);
+                HostKeep keep;
+                Scratch s(c, B * per + 16 * 64);
+                u64 *U = s.take(B * nl * N), *E = s.take(B * 2 * nl * N), *Y = s.take(B * 2 * N);
+                u64 *Z = s.take(B * 2 * l * N), *O = s.take(B * 2 * l * N);
+                std::vector<Seed> su(B), se(2 * B);
+                std::vector<u64 *> cts(B);
+                std::vector<const u64 *> pp(B);
+                for (std::size_t b = 0; b < B; ++b) {
+                    const u64 v = g.second[b0 + b];
+                    su[b] = sub_seed(m, 6, 3, v, 0);
+                    se[2 * b] = sub_seed(m, 6, 2, v, 0);
+                    se[2 * b + 1] = sub_seed(m, 6, 2, v, 1);
+                    ensure(out[v], 2 * l * N);
+                    cts[b] = out[v]->d;
+                    pp[b] = pts[v]->d;
+                }
+                sample_ternary(c, s, keep, su, U, (int)nl, true);
+                sample_noise(c, s, keep, se, E, (int)nl);
+                {  // u, both key polys and both noise polys read, both t_j written
+                    ProfScope ps(c, "k:k_rlwe/pk", 7.0 * B * nl);
+                    rlwe_pk(c, U, pk->d, K * N, E, (int)B, (int)nl);
+                }
+                {  // the last limbs' INTT (in, out), then X read, the rounding limbs written and read, OUT written
+                    ProfScope ps(c, "k:k_ntt/enc_divround", 2.0 * B * (2 + 4 * l), 4);
+                    const int pm[1] = {(int)l};
+                    for (int k = 0; k < 2; ++k)
+                        ntt_strided(c, true, E + k * nl * N + l * N, 2 * nl * N, Y + k * N, 2 * N, 1, pm, (int)B);
+                    divide_round(c, Y, 2 * N, N, PolyArr{E, 2 * nl * N, nl * N}, PolyArr{}, 0,
+                                 PolyArr{O, 2 * l * N, l * N}, (int)B, 2, (int)l, (int)l, inv.data(), inv_q.data(), Z);
+                }
+                u64 **dct = upload_ptrs(c, s, keep, cts);
+                const u64 **dpt = upload_ptrs(c, s, keep, pp);
+                {
+                    ProfScope ps(c, "k:k_rlwe/store", 5.0 * B * l);
+                    ct_store(c, O, dct, dpt, (int)B, (int)l);
+                }
+                dev_zero(c, U, B * nl * N * sizeof(u64));  // the encryption randomness
+                for (std::size_t b = 0; b < B; ++b) {
+                    hec_ciphertext *ct = out[g.second[b0 + b]];
+                    ct->size = 2;
+                    ct->level = l;
+                    ct->scale = pts[g.second[b0 + b]]->scale;
+                }
+                HEC_HIP(hipStreamSynchronize(c.stream));
+            }
+        }
     });
 }
 

@@ -138,6 +138,8 @@ struct Ctx {
     // lanes read a zero list whose fill had not landed (the round-2/4 bit mismatch);
     // HEC_KERNEL_MEMOPS=0 restores the runtime calls (A/B only)
     bool kernel_memops = true;
+    int prng_group = 0;            // option "prng_group": PRNG buffers per wavefront of k_prng (hec_keygen.hip), 1 .. 16;
+                                   // 0 picks the largest that still fills the device.  Every value draws the same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -274,6 +276,37 @@ int dec_wmax(int words);
 void decrypt_batch(Ctx &c, const u64 *const *src, const u64 *sk, int size, int level, int count, u64 *out);
 void decode_batch(Ctx &c, u64 *x, int count, int level, const u64 *crt, int wmax, const double *inv_scale,
                   double *work, u64 nv, const u32 *row, double *re, double *im);
+// KeyGenerator / Encryptor kernels (hec_keygen.hip).
+// prng_streams: stream s is SEAL's Blake2xbPRNG on seeds[s][8] (device); its words [0, nwords) go to dst[s] (a device
+// array of device pointers), one wavefront per 4096-byte buffer.  spec == nullptr stores the raw words.  Otherwise the
+// uniform sampler is fused: word g is reduced mod spec->q[g >> logN] and the words SEAL's sample_poly_uniform redraws
+// (>= spec->maxm) are listed as (s << 32 | g) in rej (rej_cap entries; *rej_n counts them all, zeroed by the caller).
+struct UniSpec {
+    u64 q[HEC_MAXL + 1], ratio[HEC_MAXL + 1], maxm[HEC_MAXL + 1];  // ratio = floor(2^64 / q)
+};
+void prng_streams(Ctx &c, const u64 *seeds, u64 *const *dst, int nstreams, u64 nwords, const UniSpec *spec, u64 *rej,
+                  u32 *rej_n, u32 rej_cap);
+// dst[pos >> 32][pos & 0xffffffff] = val, the resolved redraws
+void scatter_words(Ctx &c, u64 *const *dst, const u64 *pos, const u64 *val, int n);
+// E[s][j][i] = the centred-binomial coefficient i of stream s (bytes 6i .. 6i + 5 of raw + s raw_stride words) as a
+// residue mod q_j, j < nl
+void sample_cbd(Ctx &c, const u64 *raw, u64 raw_stride, u64 *E, int nstreams, int nl);
+// out[b][j][i] = (t[b][i] - 1) mod q_j for t in {0, 1, 2}
+void ternary_expand(Ctx &c, const u64 *t, u64 *out, int B, int nl);
+// c0 = -(c1 (*) sk + E[b]) (+ add), limbs j < nl of primes 0 .. nl - 1.  add_limb < 0: add[j][i] is added on every
+// limb (a plaintext); else add_mul * add[add_limb][i] on limb add_limb alone (a key-switching key's digit)
+struct RlweJob {
+    u64 *c0;
+    const u64 *c1, *add;
+    u64 add_mul;
+    int add_limb, pad;
+};
+void rlwe_c0(Ctx &c, const RlweJob *jobs, const u64 *sk, const u64 *E, int B, int nl);
+// E[b][k][j][i] += U[b][j][i] * pk[k][j][i], k < 2 (pk polys pk_sk words apart)
+void rlwe_pk(Ctx &c, const u64 *U, const u64 *pk, u64 pk_sk, u64 *E, int B, int nl);
+// ct[b][k][j][i] = O[b][k][j][i] (+ pt[b][j][i] for k = 0), l limbs
+void ct_store(Ctx &c, const u64 *O, u64 *const *ct, const u64 *const *pt, int B, int l);
+
 // he::fft stage kernels (hec_kernels.hip, FftIOB): the last-limb products of nsrc source entries with their stage
 // plaintexts, their rounding limbs (divide_round's pass A), and the fused multiply-rescale-sum pass that writes
 // the stage's outputs at level l - 1

@@ -20,10 +20,12 @@
 // Parity status: no SEAL-written bytes exist under /root/reference and SEAL cannot run here, so this is
 // pinned by structure tests and round trips only.
 #include <dlfcn.h>
+#include <sys/random.h>
 #include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -31,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "hec_keygen_host.h"
 #include "hecdna.h"
 
 namespace {
@@ -572,6 +575,12 @@ void emit_ciphertext(Writer &w, const CtData &c, int compr)
     d.put((u64)c.data.size());
     d.bytes(c.data.data(), c.data.size() * 8);
     close_object(m, d.b, 0);
+    if (c.seeded) {  // UniformRandomGeneratorInfo: u8 prng_type, the 64-byte seed
+        Writer g;
+        g.put(c.prng_type);
+        g.bytes(c.seed, 64);
+        close_object(m, g.b, 0);
+    }
     close_object(w, m.b, compr);
 }
 
@@ -674,6 +683,50 @@ void walk_kswitch_keys(const void *bytes, uint64_t nbytes, uint64_t max_bytes, u
 
 }  // namespace
 
+// ------------------------------------------------------------------ KeyGenerator / Encryptor randomness (host side)
+namespace hec_host {
+bool entropy_seed(uint64_t out[8])
+{
+    u8 *p = reinterpret_cast<u8 *>(out);
+    std::size_t got = 0;
+    while (got < 64) {
+        const ssize_t k = getrandom(p + got, 64 - got, 0);
+        if (k < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        got += (std::size_t)k;
+    }
+    return true;
+}
+void sub_seed(const uint64_t seed[8], uint64_t call, uint64_t role, uint64_t i, uint64_t j, uint64_t out[8])
+{
+    const u64 in[4] = {call, role, i, j};  // little-endian host
+    blake2xb(reinterpret_cast<u8 *>(out), 64, reinterpret_cast<const u8 *>(in), 32, reinterpret_cast<const u8 *>(seed),
+             64);
+}
+void redraw_walk(const uint64_t sub[8], uint64_t nwords, uint64_t N, const uint64_t *q, const uint64_t *pos,
+                 uint64_t n, uint64_t *val)
+{
+    if (!n) return;
+    PrngStream prng;
+    std::memcpy(prng.seed, sub, 64);
+    // skip the bulk draw: the continuation starts at byte 8 nwords, inside buffer 8 nwords / 4096
+    prng.counter = nwords * 8 / sizeof(prng.buf);
+    prng.refill();
+    prng.head = (std::size_t)(nwords * 8 % sizeof(prng.buf));
+    const u64 max_random = ~0ULL;
+    for (u64 k = 0; k < n; ++k) {
+        const u64 qj = q[pos[k] / N];
+        const u64 max_multiple = max_random - max_random % qj - 1;
+        u64 v;
+        do prng.generate(reinterpret_cast<u8 *>(&v), 8);
+        while (v >= max_multiple);
+        val[k] = v % qj;
+    }
+}
+}  // namespace hec_host
+
 extern "C" {
 
 const char *hec_seal_last_error(void) { return g_io_err.c_str(); }
@@ -764,6 +817,28 @@ int hec_seal_ciphertext_save(const uint64_t *data, uint64_t size, uint64_t level
         c.N = N;
         c.scale = scale;
         c.data.assign(data, data + size * level * N);
+        Writer w;
+        emit_ciphertext(w, c, compr_mode);
+        copy_out(w.b, out, cap, written);
+    });
+}
+
+int hec_seal_ciphertext_save_seeded(const uint64_t *c0, uint64_t level, uint64_t N, double scale,
+                                    const uint64_t *coeff_modulus, const uint64_t prng_seed[8], int compr_mode,
+                                    void *out, uint64_t cap, uint64_t *written)
+{
+    return io_guard([&] {
+        if (!c0 || !coeff_modulus || !prng_seed || !level || !N) throw std::invalid_argument("invalid argument");
+        CtData c;
+        parms_id_of(N, coeff_modulus, level, c.parms_id);
+        c.size = 2;
+        c.level = level;
+        c.N = N;
+        c.scale = scale;
+        c.data.assign(c0, c0 + level * N);  // c0 alone: the receiver expands c1 from the seed
+        c.seeded = true;
+        c.prng_type = 1;  // blake2xb
+        std::memcpy(c.seed, prng_seed, 64);
         Writer w;
         emit_ciphertext(w, c, compr_mode);
         copy_out(w.b, out, cap, written);

@@ -74,14 +74,15 @@ int hec_context_synchronize(hec_context *ctx);
  * data targets' fused MAC kernel divides-and-rounds its own accumulators; 0: the separate divide-and-round pass B;
  * HEC_MAC_DIVROUND at context creation, HEC_EINVAL when out of range), "kernel_memops" (0: workspace fills and
  * device copies through the runtime's hipMemsetAsync / hipMemcpyAsync instead of engine kernels; A/B only,
- * DESIGN.md §4.8), and three debug switches:
+ * DESIGN.md §4.8), "prng_group" (0..16: PRNG buffers per wavefront of the key generator's BLAKE2Xb kernel, 0 = chosen per
+ * launch; every value draws the same words), and three debug switches:
  * "poison" (every workspace carve and fresh output buffer is filled with 0xFF bytes before use, so a read of
  * memory the call never wrote becomes a deterministic wrong result), "lane_serial" (batch lanes run one after
  * another) and "debug_lanes" (per-call zero-list and key-table reports on stderr).  Every schedule is
  * bit-identical.  Applies to the context and its batch lanes; HEC_EINVAL for an unknown name, and for a value
  * outside an enumerated knob's range ("split_bfly" 0..4, "hmac" 0..2, "hmac_odd3" 0..1, "hoist_scan" 0..1,
  * "nttb_shfl" 0..2, "nttb_shfl_dr" 0..1, "moddown1" 0..1, "hmac_int" 0..1, "nt_e" 0..1,
- * "mac_divround" 0..1). */
+ * "mac_divround" 0..1, "prng_group" 0..16). */
 int hec_context_set_option(hec_context *ctx, const char *name, int64_t value);
 uint64_t hec_context_poly_degree(const hec_context *ctx);
 uint64_t hec_context_key_moduli(const hec_context *ctx); /* K */
@@ -164,6 +165,55 @@ int hec_decode(hec_context *ctx, const hec_plaintext *const *pts, uint64_t count
 /* both in one pass, with no plaintext objects in between; the doubles are those of hec_decode(hec_decrypt()) */
 int hec_decrypt_decode(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
                        uint64_t n_values, double *re, double *im);
+
+/* ---------------------------------------------------------------- KeyGenerator / Encryptor -- */
+/* The first lines of every reference demo (matrix_operations.cpp:1057-1065, client.cpp:87-115): KeyGenerator's
+ * secret_key / create_public_key / create_relin_keys / create_galois_keys and Encryptor's encrypt /
+ * encrypt_symmetric, generated on the GPU.
+ *
+ * Randomness.  Every generating call takes `seed`, a 64-byte SEAL prng_seed_type.  NULL draws 64 bytes from
+ * getrandom(2) (HEC_ELOGIC when that fails; there is no time or pid fallback).  With a given seed the call's output
+ * is a pure function of its arguments.  A SEED MUST NEVER BE REUSED ACROSS CALLS: two calls with one seed share their
+ * sub-streams (the same `a` and the same noise), which reveals the difference of their plaintexts or keys.  Derive a
+ * fresh seed per call (hecdna/seal_compat.hpp hashes a master seed with a call counter).
+ * Sub-stream (call, role, i, j) is SEAL's Blake2xbPRNG on the 64-byte value BLAKE2Xb(input = the four values as
+ * little-endian u64, key = seed, 64 bytes) = hec_seal_blake2xb; call 1 secret, 2 public key, 3 relin, 4 galois,
+ * 5 encrypt_symmetric, 6 encrypt; role 1 the uniform `a`, 2 the noise `e`, 3 a ternary polynomial; (i, j) = relin
+ * (digit, 0), galois (digit, galois_elt), encrypt_symmetric (batch index, 0), encrypt (batch index, 0) for u and e_0
+ * and (batch index, 1) for e_1.  `a` is SEAL's sample_poly_uniform over the stream (what a seeded ciphertext's
+ * receiver expands); a ternary polynomial is the same routine with the modulus 3 over N words, coefficient
+ * (v mod 3) - 1; the noise is the centred binomial of SEAL 4.1's sample_poly_cbd (6 bytes per coefficient, in
+ * [-21, 21]).  SEAL's own ternary stream and noise stream cannot be observed by any caller and are not reproduced.
+ *
+ * An RLWE sample over the primes S is c1 = a (used as drawn, NTT form), c0 = -(a s + NTT(e)).  Nothing is written on
+ * an error.  Errors as SEAL: "secret key is not valid for encryption parameters", "public key is not valid for
+ * encryption parameters", "plain is not valid for encryption parameters", "Galois element is not valid". */
+typedef struct hec_public_key hec_public_key; /* seal::PublicKey: u64[2][K][N], NTT form, key level */
+/* KeyGenerator::secret_key(): a ternary s, its residues on all K primes, NTT form */
+int hec_keygen_secret(hec_context *ctx, const uint64_t seed[8], hec_secret_key **out);
+/* KeyGenerator::create_public_key: one RLWE sample over all K primes */
+int hec_keygen_public(hec_context *ctx, const hec_secret_key *sk, const uint64_t seed[8], hec_public_key **out);
+int hec_public_key_upload(hec_context *ctx, const uint64_t *host, hec_public_key **out); /* u64[2][K][N] */
+int hec_public_key_download(const hec_public_key *pk, uint64_t *host);                  /* synchronises */
+int hec_public_key_destroy(hec_public_key *pk);
+/* KeyGenerator::create_relin_keys (generate_one_kswitch_key): digit J is an RLWE sample over all K primes with
+ * (P mod q_J) (s (*) s) added to limb J of c0; layout u64[L][2][K][N] */
+int hec_keygen_relin(hec_context *ctx, const hec_secret_key *sk, const uint64_t seed[8], hec_kswitch_key **out);
+/* KeyGenerator::create_galois_keys(elts): the same with apply_galois_ntt(s, elt) in place of s (*) s, for n
+ * elements (n == 0: the set of hec_default_galois_elts); a key's words do not depend on the other elements asked
+ * for.  The keys land as hec_galois_keys_add leaves them. */
+int hec_keygen_galois(hec_galois_keys *gk, const hec_secret_key *sk, const uint32_t *elts, uint64_t n,
+                      const uint64_t seed[8]);
+/* Encryptor::encrypt_symmetric for `count` plaintexts (levels may differ): out[v] = an RLWE sample over the
+ * plaintext's primes with the plaintext added to c0, at the plaintext's level and scale.  public_seeds (count * 8
+ * words, or NULL) receives the sub-seed of every `a`, what hec_seal_ciphertext_save_seeded writes. */
+int hec_encrypt_symmetric(hec_context *ctx, const hec_secret_key *sk, const hec_plaintext *const *pts, uint64_t count,
+                          const uint64_t seed[8], hec_ciphertext *const *out, uint64_t *public_seeds);
+/* Encryptor::encrypt (encrypt_zero_internal, asymmetric) for a plaintext at level l: over the l + 1 primes of the
+ * level above (l = L: all K primes), t_j = u (*) pk_j + NTT(e_j) with u ternary, each t_j divided and rounded by the
+ * last of these primes (the arithmetic of hec_rescale_to_next_inplace; the scale is left alone), then c0 += plain. */
+int hec_encrypt(hec_context *ctx, const hec_public_key *pk, const hec_plaintext *const *pts, uint64_t count,
+                const uint64_t seed[8], hec_ciphertext *const *out);
 
 /* ---------------------------------------------------------------- keys -------------------- */
 /* RelinKeys (KeyGenerator::create_relin_keys, matrix_operations.cpp:1061-1062): data u64[L][2][K][N] */
@@ -361,6 +411,12 @@ int hec_seal_shake256(const void *in, uint64_t nbytes, uint64_t outlen, void *ou
 int hec_seal_ciphertext_save(const uint64_t *data, uint64_t size, uint64_t level, uint64_t poly_modulus_degree,
                              double scale, const uint64_t *coeff_modulus, int compr_mode, void *out, uint64_t cap,
                              uint64_t *written);
+/* Serializable<Ciphertext>::save of Encryptor::encrypt_symmetric(plain) (client.cpp:113-114), host only: c0
+ * (u64[level][N]) and the UniformRandomGeneratorInfo {prng_type 1 (blake2xb), prng_seed} that Ciphertext::expand_seed
+ * and hec_seal_ciphertext_load_ex expand into c1; prng_seed = the public_seeds entry of hec_encrypt_symmetric. */
+int hec_seal_ciphertext_save_seeded(const uint64_t *c0, uint64_t level, uint64_t poly_modulus_degree, double scale,
+                                    const uint64_t *coeff_modulus, const uint64_t prng_seed[8], int compr_mode,
+                                    void *out, uint64_t cap, uint64_t *written);
 /* EncryptionParameters::load / save (CKKS) */
 int hec_seal_parms_load(const void *bytes, uint64_t nbytes, uint64_t *poly_modulus_degree, uint64_t *coeff_modulus,
                         uint64_t cap, uint64_t *count, uint64_t *consumed);
