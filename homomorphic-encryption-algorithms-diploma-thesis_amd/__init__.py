@@ -882,20 +882,30 @@ class DeviceBuffer:
             pass
 
 
-class Ciphertext:
+class _DeviceObject:
+    """A device object of a context: its context, its C handle `h` and the name of the C call that destroys it.  The
+    object may be finalised before or after its context, on any thread (hecdna.h)."""
+    _destroy = None
+    ctx = None
+    h = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                getattr(lib(), self._destroy)(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class Ciphertext(_DeviceObject):
+    _destroy = "hec_ciphertext_destroy"
+
     def __init__(self, ctx: Context):
         self.ctx = ctx
         h = C.c_void_p()
         _check(lib().hec_ciphertext_create(ctx.h, C.byref(h)))
         self.h = h
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_ciphertext_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
     def upload(self, data: np.ndarray, scale: float):
         a = np.ascontiguousarray(data, dtype=np.uint64)
@@ -930,6 +940,8 @@ class Ciphertext:
         return self
 
     def copy(self):
+        if not self.ctx.h:  # closed: hec_ciphertext_copy's answer, before a destination is asked of no context
+            raise InvalidArgument(HEC_EINVAL, "encrypted is not valid for encryption parameters")
         c = Ciphertext(self.ctx)
         _check(lib().hec_ciphertext_copy(c.h, self.h))
         return c
@@ -949,7 +961,9 @@ class Ciphertext:
         return buf.raw[: n.value]
 
 
-class Plaintext:
+class Plaintext(_DeviceObject):
+    _destroy = "hec_plaintext_destroy"
+
     def __init__(self, ctx: Context, data, scale):
         self.ctx = ctx
         h = C.c_void_p()
@@ -974,17 +988,10 @@ class Plaintext:
         _check(lib().hec_plaintext_download(self.h, _p(out)))
         return out
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_plaintext_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
-
-class SecretKey:
+class SecretKey(_DeviceObject):
     """seal::SecretKey on the device: u64[K][N], NTT form at the key level; wiped when destroyed."""
+    _destroy = "hec_secret_key_destroy"
 
     def __init__(self, ctx: Context, data, handle=None):
         self.ctx = ctx
@@ -1003,17 +1010,10 @@ class SecretKey:
         _check(lib().hec_secret_key_download(self.h, _p(a)))
         return a
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_secret_key_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
-
-class PublicKey:
+class PublicKey(_DeviceObject):
     """seal::PublicKey on the device: u64[2][K][N], NTT form at the key level."""
+    _destroy = "hec_public_key_destroy"
 
     def __init__(self, ctx: Context, data, handle=None):
         self.ctx = ctx
@@ -1033,16 +1033,10 @@ class PublicKey:
         _check(lib().hec_public_key_download(self.h, _p(a)))
         return a
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_public_key_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
+class KSwitchKey(_DeviceObject):
+    _destroy = "hec_kswitch_key_destroy"
 
-class KSwitchKey:
     def __init__(self, ctx: Context, data=None, seed=None, seal_bytes: bytes | None = None, handle=None):
         self.ctx = ctx
         h = C.c_void_p()
@@ -1066,16 +1060,10 @@ class KSwitchKey:
         _check(lib().hec_kswitch_key_download(self.h, _p(a)))
         return a
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_kswitch_key_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
+class GaloisKeys(_DeviceObject):
+    _destroy = "hec_galois_keys_destroy"
 
-class GaloisKeys:
     def __init__(self, ctx: Context):
         self.ctx = ctx
         h = C.c_void_p()
@@ -1108,11 +1096,3 @@ class GaloisKeys:
         else:
             _check(lib().hec_galois_keys_load_seal_ex(self.h, C.c_char_p(b), len(b), int(max_lists), C.byref(used)))
         return used.value
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().hec_galois_keys_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <exception>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <thread>
@@ -28,6 +29,7 @@
 
 #include "hec_internal.h"
 #include "hec_keygen_host.h"
+#include "hec_live.h"
 
 #include <array>
 #include <dlfcn.h>
@@ -61,67 +63,38 @@ struct hec_context {
     // multi-GPU (hec_comm_init): this process's rank in a world of one process per GPU, RCCL communicator
     int rank = 0, world = 1;
     HecComm *comm = nullptr;
-    u64 gen = 0;  // this context's entry in the live-context registry (ctx_alive)
+    u64 gen = 0;  // this context's entry in the live-context registry (hec_live.h)
 };
-// Objects may outlive their context (SEAL's objects hold their context by shared_ptr, so a caller may free them in
-// any order, and a garbage collector finalising a reference cycle picks its own order): every object records its
-// context's generation, and its destroy touches the context (device, stream) only while that context is alive.
-// An address reused by a later context carries a new generation, so it is never mistaken for the old one.
-static std::mutex g_live_mu;
-static std::map<const hec_context *, u64> g_live;
-static u64 g_live_gen = 0;
-static u64 ctx_register(const hec_context *c)
-{
-    std::lock_guard<std::mutex> lock(g_live_mu);
-    return g_live[c] = ++g_live_gen;
-}
-static void ctx_unregister(const hec_context *c)
-{
-    std::lock_guard<std::mutex> lock(g_live_mu);
-    g_live.erase(c);
-}
-static bool ctx_alive(const hec_context *c, u64 gen)
-{
-    std::lock_guard<std::mutex> lock(g_live_mu);
-    const auto it = g_live.find(c);
-    return c && it != g_live.end() && it->second == gen;
-}
-struct hec_ciphertext {
+// Every device object records its context by address and generation (hec_live.h) and its device, so that its destroy
+// can free its memory after the context is gone.  bind() is the only place that sets these.
+struct DevObject {
     hec_context *ctx = nullptr;
     u64 ctx_gen = 0;
+    int device = 0;
+};
+struct hec_ciphertext : DevObject {
     u64 *d = nullptr;
     std::size_t cap = 0;  // words
     std::size_t size = 0, level = 0;
     double scale = 1.0;
 };
-struct hec_plaintext {
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
+struct hec_plaintext : DevObject {
     u64 *d = nullptr;
     std::size_t cap = 0;
     std::size_t level = 0;
     double scale = 1.0;
 };
-struct hec_kswitch_key {
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
+struct hec_kswitch_key : DevObject {
     u64 *d = nullptr;
 };
-struct hec_secret_key {  // seal::SecretKey: u64[K][N], NTT form, key level
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
-    int device = 0;  // for the wipe of a key that outlives its context
+struct hec_secret_key : DevObject {  // seal::SecretKey: u64[K][N], NTT form, key level
     u64 *d = nullptr;
     std::size_t words = 0;
 };
-struct hec_public_key {  // seal::PublicKey: u64[2][K][N], NTT form, key level
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
+struct hec_public_key : DevObject {  // seal::PublicKey: u64[2][K][N], NTT form, key level
     u64 *d = nullptr;
 };
-struct hec_galois_keys {
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
+struct hec_galois_keys : DevObject {
     std::map<u32, u64 *> keys;
     std::map<u32, u64 *> negw;  // hoisted mod-up: W_elt[I] = NTT_I(sign mask of elt), built on first use
     // hoisted MAC: KW[elt, l][k][I] = sum_{J<l, J!=I} (q_J mod q_I) key_elt[J][k][I] mod q_I, built on first
@@ -296,14 +269,6 @@ u64 *dalloc(std::size_t words)
     if (words == 0) words = 1;
     HEC_HIP(hipMalloc(&p, words * sizeof(u64)));
     return (u64 *)p;
-}
-void ensure(hec_ciphertext *ct, std::size_t words)
-{
-    if (ct->cap >= words) return;
-    if (ct->d) HEC_HIP(hipFree(ct->d));
-    ct->d = dalloc(words);
-    ct->cap = words;
-    if (ct->ctx && ct->ctx->c.poison) dev_fill(ct->ctx->c, ct->d, 0xFFFFFFFFu, words * sizeof(u64));
 }
 
 // stack-style carving of the context workspace; kernels are stream ordered, so a region released
@@ -736,12 +701,6 @@ std::size_t rescale_words(const Ctx &c, std::size_t B, std::size_t nk, std::size
     return c.N * B * nk * (1 + 2 * l) + 3 * 64;
 }
 
-void check_ct(const hec_context *ctx, const hec_ciphertext *a)
-{
-    need(a && a->ctx == ctx, "encrypted is not valid for encryption parameters");
-    need(a->level >= 1 && a->level <= ctx->c.L && a->size >= 2 && a->d,
-         "encrypted is not valid for encryption parameters");
-}
 void set_device(hec_context *ctx)
 {
     need(ctx != nullptr, "context is null");
@@ -753,6 +712,135 @@ void d2d(Ctx &c, void *dst, const void *src, std::size_t words)
     if (!words) return;
     if (c.kernel_memops) dev_copy64(c, (u64 *)dst, (const u64 *)src, words);
     else HEC_HIP(hipMemcpyAsync(dst, src, words * sizeof(u64), hipMemcpyDeviceToDevice, c.stream));
+}
+
+// ------------------------------------------------------------------ device objects ---------
+// SEAL's is_valid_for messages, one per object kind
+constexpr const char *BAD_CT = "encrypted is not valid for encryption parameters";
+constexpr const char *BAD_PLAIN = "plain is not valid for encryption parameters";
+constexpr const char *BAD_SK = "secret key is not valid for encryption parameters";
+constexpr const char *BAD_PK = "public key is not valid for encryption parameters";
+constexpr const char *BAD_RK = "relin_keys is not valid for encryption parameters";
+constexpr const char *BAD_GK = "galois_keys is not valid for encryption parameters";
+
+void bind(DevObject &o, hec_context *ctx)
+{
+    o.ctx = ctx;
+    o.ctx_gen = ctx->gen;
+    o.device = ctx->c.device;
+}
+// A new object of ctx, owned until the constructor releases it into *out: a constructor that throws destroys it.
+template <class T, int (*Destroy)(T *)>
+auto make(hec_context *ctx)
+{
+    struct Del {
+        void operator()(T *o) const { (void)Destroy(o); }
+    };
+    std::unique_ptr<T, Del> o(new T());
+    bind(*o, ctx);
+    return o;
+}
+
+// Calls that take a context: the object must belong to this very context (a later context at the same address has
+// another generation).
+void check_obj(const hec_context *ctx, const DevObject *o, const char *msg)
+{
+    need(o && o->ctx == ctx && o->ctx_gen == ctx->gen, msg);
+}
+void check_ct(const hec_context *ctx, const hec_ciphertext *a)
+{
+    check_obj(ctx, a, BAD_CT);
+    need(a->level >= 1 && a->level <= ctx->c.L && a->size >= 2 && a->d, BAD_CT);
+}
+void check_plain_data(const hec_context *ctx, const hec_plaintext *p)  // holds data; the caller compares the level
+{
+    check_obj(ctx, p, BAD_PLAIN);
+    need(p->d != nullptr, BAD_PLAIN);
+}
+void check_plain(const hec_context *ctx, const hec_plaintext *p)
+{
+    check_plain_data(ctx, p);
+    need(p->level >= 1 && p->level <= ctx->c.L, BAD_PLAIN);
+}
+void check_pk(const hec_context *ctx, const hec_public_key *pk)
+{
+    check_obj(ctx, pk, BAD_PK);
+    need(pk->d != nullptr, BAD_PK);
+}
+// Calls that take an object and no context: the object's context must still exist, checked before anything is read
+// through o->ctx; selects its device.  The registry lock is not held across the caller's work: one host thread
+// drives a context (hecdna.h), only destroys arrive from other threads.
+Ctx &live(const DevObject *o, const char *msg)
+{
+    need(hec_live::while_alive(o->ctx, o->ctx_gen, [] {}), msg);
+    set_device(o->ctx);
+    return o->ctx->c;
+}
+
+// A ciphertext's or plaintext's buffer of at least `words` words: at once when the capacity suffices (a warmed-up
+// loop never waits here), else a new buffer holding the first keep_words words of the old one, the rest poisoned
+// under c.poison.  The old buffer goes only after the context's stream has drained: enqueued work may still read it.
+template <class T>
+void grow(T *o, std::size_t words, std::size_t keep_words = 0)
+{
+    if (o->cap >= words) return;
+    Ctx &c = o->ctx->c;
+    u64 *nd = keep_words ? dalloc(words) : nullptr;
+    if (keep_words) d2d(c, nd, o->d, keep_words);
+    if (o->d) {
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        HEC_HIP(hipFree(o->d));
+        o->d = nullptr;
+        o->cap = 0;
+    }
+    o->d = nd ? nd : dalloc(words);
+    o->cap = words;
+    if (c.poison) dev_fill(c, o->d + keep_words, 0xFFFFFFFFu, (words - keep_words) * sizeof(u64));
+}
+
+// The device memory an object owns
+template <class T>
+std::vector<u64 *> owned(const T &o)
+{
+    return {o.d};
+}
+std::vector<u64 *> owned(const hec_galois_keys &gk)
+{
+    std::vector<u64 *> v;
+    for (const auto &kv : gk.keys) v.push_back(kv.second);
+    for (const auto &kv : gk.negw) v.push_back(kv.second);
+    for (const auto &kv : gk.kw) v.push_back(kv.second);
+    for (const auto &kv : gk.mkey) v.push_back(kv.second);
+    return v;
+}
+// The one destroy.  On the object's device: while its context lives, drain the context's stream (enqueued work may
+// still read the object), then free what the object owns; after its context the object frees its own memory and
+// touches nothing else.  wipe_words: SEAL wipes a secret key's memory when it goes, so that many words are
+// zero-filled first with the engine's fill kernel, on the context's stream or else on the device's null stream.
+template <class T>
+int release(T *o, std::size_t wipe_words = 0)
+{
+    return guard([&] {
+        if (!o) return;
+        (void)hipSetDevice(o->device);
+        const std::vector<u64 *> mem = owned(*o);
+        auto drain = [&](hipStream_t st) {
+            try {
+                if (wipe_words) {
+                    Ctx wipe;
+                    wipe.stream = st;
+                    dev_fill32(wipe, mem[0], 0, wipe_words * sizeof(u64));
+                }
+            } catch (...) {  // the memory is freed all the same
+            }
+            (void)hipStreamSynchronize(st);
+        };
+        const bool holds = std::any_of(mem.begin(), mem.end(), [](const u64 *p) { return p != nullptr; });
+        const bool alive = holds && hec_live::while_alive(o->ctx, o->ctx_gen, [&] { drain(o->ctx->c.stream); });
+        if (holds && !alive && wipe_words) drain(nullptr);
+        for (u64 *p : mem) (void)hipFree(p);
+        delete o;
+    });
 }
 
 // ------------------------------------------------------------------ he::linalg driver -----
@@ -932,15 +1020,14 @@ std::vector<double> matvec_check(hec_context *ctx, const hec_ciphertext *const *
     const bool pt = pdiags != nullptr;
     need(n >= 1 && p >= 1 && !js.empty(), "empty matrix operand");
     for (std::size_t j : js) need(j < n, "diagonal index out of range");
-    need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
-    if (finish && !pt) need(rk && rk->ctx == ctx, "relin_keys is not valid for encryption parameters");
+    check_obj(ctx, gk, BAD_GK);
+    if (finish && !pt) check_obj(ctx, rk, BAD_RK);
     const std::size_t l = cols[0]->level;
     for (std::size_t i = 0; i < p; ++i) check_ct(ctx, cols[i]);
     for (std::size_t i = 0; i < p; ++i) need(cols[i]->size == 2, "encrypted size must be 2");
     for (std::size_t i = 0; i < p; ++i) need(cols[i]->level == l, "encrypted1 and encrypted2 parameter mismatch");
     if (pt) {
-        for (std::size_t j : js)
-            need(pdiags[j] && pdiags[j]->ctx == ctx && pdiags[j]->d, "plain is not valid for encryption parameters");
+        for (std::size_t j : js) check_plain_data(ctx, pdiags[j]);
         for (std::size_t j : js) need(pdiags[j]->level == l, "encrypted_ntt and plain_ntt parameter mismatch");
     } else {
         for (std::size_t j : js) check_ct(ctx, diags[j]);
@@ -1073,7 +1160,7 @@ void matvec_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec
     const u64 accw = pt ? S2 : S3;  // accumulator words per output
     if (!finish) {
         for (std::size_t i = 0; i < p; ++i) {
-            ensure(out[i], accw);
+            grow(out[i], accw);
             d2d(c, out[i]->d, ACC3 + i * S3, accw);
             out[i]->size = pt ? 2 : 3; out[i]->level = l; out[i]->scale = ps[i];
         }
@@ -1088,7 +1175,7 @@ void matvec_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec
     rescale_batch(c, s, Aa, (int)p, 2, (int)l, PolyArr{O, So, (l - 1) * N});
     const double ql = (double)c.q[l - 1];
     for (std::size_t i = 0; i < p; ++i) {
-        ensure(out[i], So);
+        grow(out[i], So);
         d2d(c, out[i]->d, O + i * So, So);
         out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = ps[i] / ql;
     }
@@ -1204,13 +1291,13 @@ void matvec_lanes(hec_context *ctx, const hec_ciphertext *const *diags, const he
         }
     }
     // the outputs are sized here, on the calling thread, so no lane thread frees or allocates them (matvec_core's
-    // ensure() then finds them large enough)
+    // grow() then finds them large enough)
     {
         const std::size_t l = cols[0]->level, N = c.N;
         const std::size_t w = finish ? 2 * (l - 1) * N : (pdiags ? 2 : 3) * l * N;
         for (std::size_t i = 0; i < p; ++i) {
             need(out[i] != nullptr, "null argument");
-            ensure(out[i], w);
+            grow(out[i], w);
         }
     }
     while ((int)ctx->lanes.size() < nl) ctx->lanes.push_back(make_lane(ctx));
@@ -1701,7 +1788,7 @@ int hec_context_create(uint64_t N, const uint64_t *mod, uint64_t K, int device, 
         // the tables went up with blocking copies on the null stream, which the non-blocking context stream does
         // not wait for: finish them before any kernel can read them
         HEC_HIP(hipDeviceSynchronize());
-        ctx->gen = ctx_register(ctx);
+        ctx->gen = hec_live::ctx_register(ctx);
         *out = ctx;
     });
 }
@@ -1710,7 +1797,7 @@ int hec_context_destroy(hec_context *ctx)
 {
     return guard([&] {
         if (!ctx) return;
-        ctx_unregister(ctx);
+        hec_live::ctx_unregister(ctx);  // waits for a destroy that is draining this context's stream
         Ctx &c = ctx->c;
         (void)hipSetDevice(c.device);
         (void)hipStreamSynchronize(c.stream);
@@ -1846,35 +1933,18 @@ int hec_ciphertext_create(hec_context *ctx, hec_ciphertext **out)
 {
     return guard([&] {
         need(ctx && out, "null argument");
-        auto *ct = new hec_ciphertext();
-        ct->ctx = ctx;
-        ct->ctx_gen = ctx->gen;
-        *out = ct;
+        *out = make<hec_ciphertext, hec_ciphertext_destroy>(ctx).release();
     });
 }
-int hec_ciphertext_destroy(hec_ciphertext *ct)
-{
-    return guard([&] {
-        if (!ct) return;
-        if (ct->d) {
-            if (ctx_alive(ct->ctx, ct->ctx_gen)) {
-                (void)hipSetDevice(ct->ctx->c.device);
-                (void)hipStreamSynchronize(ct->ctx->c.stream);
-            }
-            (void)hipFree(ct->d);
-        }
-        delete ct;
-    });
-}
+int hec_ciphertext_destroy(hec_ciphertext *ct) { return release(ct); }
 int hec_ciphertext_upload(hec_ciphertext *ct, const uint64_t *host, uint64_t size, uint64_t level, double scale)
 {
     return guard([&] {
         need(ct && host, "null argument");
-        Ctx &c = ct->ctx->c;
-        set_device(ct->ctx);
-        need(size >= 1 && level >= 1 && level <= c.K, "encrypted is not valid for encryption parameters");
+        Ctx &c = live(ct, BAD_CT);
+        need(size >= 1 && level >= 1 && level <= c.K, BAD_CT);
         const std::size_t w = size * level * c.N;
-        ensure(ct, w);
+        grow(ct, w);
         HEC_HIP(hipMemcpyAsync(ct->d, host, w * sizeof(u64), hipMemcpyHostToDevice, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
         ct->size = size; ct->level = level; ct->scale = scale;
@@ -1884,8 +1954,7 @@ int hec_ciphertext_download(const hec_ciphertext *ct, uint64_t *host)
 {
     return guard([&] {
         need(ct && host && ct->d, "null argument");
-        Ctx &c = ct->ctx->c;
-        set_device(ct->ctx);
+        Ctx &c = live(ct, BAD_CT);
         const std::size_t w = ct->size * ct->level * c.N;
         HEC_HIP(hipMemcpyAsync(host, ct->d, w * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
@@ -1903,12 +1972,12 @@ int hec_ciphertext_info(const hec_ciphertext *ct, uint64_t *size, uint64_t *leve
 int hec_ciphertext_copy(hec_ciphertext *dst, const hec_ciphertext *src)
 {
     return guard([&] {
-        need(dst && src && dst->ctx == src->ctx, "null argument");
-        set_device(dst->ctx);
+        need(dst && src && dst->ctx == src->ctx && dst->ctx_gen == src->ctx_gen, "null argument");
+        Ctx &c = live(dst, BAD_CT);
         if (dst == src) return;
-        const std::size_t w = src->size * src->level * src->ctx->c.N;
-        ensure(dst, w);
-        d2d(src->ctx->c, dst->d, src->d, w);
+        const std::size_t w = src->size * src->level * c.N;
+        grow(dst, w);
+        d2d(c, dst->d, src->d, w);
         dst->size = src->size; dst->level = src->level; dst->scale = src->scale;
     });
 }
@@ -1916,18 +1985,18 @@ int hec_ciphertext_export_device(const hec_ciphertext *ct, void *dev_dst)
 {
     return guard([&] {
         need(ct && dev_dst && ct->d, "null argument");
-        set_device(ct->ctx);
-        d2d(ct->ctx->c, dev_dst, ct->d, ct->size * ct->level * ct->ctx->c.N);
+        Ctx &c = live(ct, BAD_CT);
+        d2d(c, dev_dst, ct->d, ct->size * ct->level * c.N);
     });
 }
 int hec_ciphertext_import_device(hec_ciphertext *ct, const void *dev_src, uint64_t size, uint64_t level, double scale)
 {
     return guard([&] {
         need(ct && dev_src, "null argument");
-        set_device(ct->ctx);
-        const std::size_t w = size * level * ct->ctx->c.N;
-        ensure(ct, w);
-        d2d(ct->ctx->c, ct->d, dev_src, w);
+        Ctx &c = live(ct, BAD_CT);
+        const std::size_t w = size * level * c.N;
+        grow(ct, w);
+        d2d(c, ct->d, dev_src, w);
         ct->size = size; ct->level = level; ct->scale = scale;
     });
 }
@@ -1943,10 +2012,9 @@ int hec_ciphertext_fill_uniform(hec_ciphertext *ct, uint64_t size, uint64_t leve
 {
     return guard([&] {
         need(ct != nullptr, "null argument");
-        Ctx &c = ct->ctx->c;
-        set_device(ct->ctx);
-        need(size >= 1 && level >= 1 && level <= c.L, "encrypted is not valid for encryption parameters");
-        ensure(ct, size * level * c.N);
+        Ctx &c = live(ct, BAD_CT);
+        need(size >= 1 && level >= 1 && level <= c.L, BAD_CT);
+        grow(ct, size * level * c.N);
         fill_uniform(c, ct->d, (int)size, (int)level, 0, 0, seed);
         ct->size = size; ct->level = level; ct->scale = scale;
     });
@@ -1956,36 +2024,17 @@ int hec_plaintext_create(hec_context *ctx, hec_plaintext **out)
 {
     return guard([&] {
         need(ctx && out, "null argument");
-        auto *p = new hec_plaintext();
-        p->ctx = ctx;
-        p->ctx_gen = ctx->gen;
-        *out = p;
+        *out = make<hec_plaintext, hec_plaintext_destroy>(ctx).release();
     });
 }
-int hec_plaintext_destroy(hec_plaintext *pt)
-{
-    return guard([&] {
-        if (!pt) return;
-        if (pt->d) {
-            if (ctx_alive(pt->ctx, pt->ctx_gen)) (void)hipStreamSynchronize(pt->ctx->c.stream);
-            (void)hipFree(pt->d);
-        }
-        delete pt;
-    });
-}
+int hec_plaintext_destroy(hec_plaintext *pt) { return release(pt); }
 int hec_plaintext_fill_uniform(hec_plaintext *pt, uint64_t level, double scale, uint64_t seed)
 {
     return guard([&] {
         need(pt != nullptr, "null argument");
-        Ctx &c = pt->ctx->c;
-        set_device(pt->ctx);
-        need(level >= 1 && level <= c.L, "plain is not valid for encryption parameters");
-        const std::size_t w = level * c.N;
-        if (pt->cap < w) {
-            if (pt->d) HEC_HIP(hipFree(pt->d));
-            pt->d = dalloc(w);
-            pt->cap = w;
-        }
+        Ctx &c = live(pt, BAD_PLAIN);
+        need(level >= 1 && level <= c.L, BAD_PLAIN);
+        grow(pt, level * c.N);
         fill_uniform(c, pt->d, 1, (int)level, 0, 0, seed);
         pt->level = level; pt->scale = scale;
     });
@@ -1995,15 +2044,10 @@ int hec_plaintext_upload(hec_plaintext *pt, const uint64_t *host, uint64_t level
 {
     return guard([&] {
         need(pt && host, "null argument");
-        Ctx &c = pt->ctx->c;
-        set_device(pt->ctx);
-        need(level >= 1 && level <= c.L, "plain is not valid for encryption parameters");
+        Ctx &c = live(pt, BAD_PLAIN);
+        need(level >= 1 && level <= c.L, BAD_PLAIN);
         const std::size_t w = level * c.N;
-        if (pt->cap < w) {
-            if (pt->d) HEC_HIP(hipFree(pt->d));
-            pt->d = dalloc(w);
-            pt->cap = w;
-        }
+        grow(pt, w);
         HEC_HIP(hipMemcpyAsync(pt->d, host, w * sizeof(u64), hipMemcpyHostToDevice, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
         pt->level = level; pt->scale = scale;
@@ -2014,9 +2058,8 @@ int hec_plaintext_download(const hec_plaintext *pt, uint64_t *host)
 {
     return guard([&] {
         need(pt && host, "null argument");
-        need(pt->d != nullptr, "plain is not valid for encryption parameters");
-        Ctx &c = pt->ctx->c;
-        set_device(pt->ctx);
+        need(pt->d != nullptr, BAD_PLAIN);
+        Ctx &c = live(pt, BAD_PLAIN);
         HEC_HIP(hipMemcpyAsync(host, pt->d, pt->level * c.N * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
     });
@@ -2106,7 +2149,7 @@ int hec_encode(hec_context *ctx, const double *re, const double *im, uint64_t n_
         if (n_values > c.N / 2) throw std::invalid_argument("values has invalid size");
         if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
         if (scale <= 0 || (int)std::log2(scale) >= c.total_bits(level)) throw std::invalid_argument("scale out of bounds");
-        for (u64 v = 0; v < count; ++v) need(out[v] && out[v]->ctx == ctx, "plain is not valid for encryption parameters");
+        for (u64 v = 0; v < count; ++v) check_obj(ctx, out[v], BAD_PLAIN);
         if (count == 0) return;
         encoder_tables(c);
         const u64 N = c.N, nv = n_values;
@@ -2142,11 +2185,7 @@ int hec_encode(hec_context *ctx, const double *re, const double *im, uint64_t n_
             for (u64 v = 0; v < cnt; ++v) {
                 hec_plaintext *pt = out[v0 + v];
                 const std::size_t w = level * N;
-                if (pt->cap < w) {
-                    if (pt->d) HEC_HIP(hipFree(pt->d));
-                    pt->d = dalloc(w);
-                    pt->cap = w;
-                }
+                grow(pt, w);
                 d2d(c, pt->d, res + v * w, w);
                 pt->level = level;
                 pt->scale = scale;
@@ -2200,16 +2239,11 @@ int hec_encode_scalar(hec_context *ctx, double value, double scale, uint64_t lev
         Ctx &c = ctx->c;
         set_device(ctx);
         if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        need(out->ctx == ctx, "plain is not valid for encryption parameters");
+        check_obj(ctx, out, BAD_PLAIN);
         u64 words[HEC_MAXL + 1];
         scalar_words(c, value, scale, level, words);
         // the constant polynomial in NTT form: every coefficient of limb j is the residue (SEAL's fill_n)
-        const std::size_t w = level * c.N;
-        if (out->cap < w) {
-            if (out->d) HEC_HIP(hipFree(out->d));
-            out->d = dalloc(w);
-            out->cap = w;
-        }
+        grow(out, level * c.N);
         fill_limbs(c, out->d, (int)level, words);
         out->level = level;
         out->scale = scale;
@@ -2361,11 +2395,7 @@ void dec_run(hec_context *ctx, const u64 *sk, const std::vector<DecEntry> &in, h
                 for (std::size_t j = 0; j < n; ++j) {
                     hec_plaintext *pt = pts[v0 + g.second[j]];
                     const std::size_t w = level * N;
-                    if (pt->cap < w) {
-                        if (pt->d) HEC_HIP(hipFree(pt->d));
-                        pt->d = dalloc(w);
-                        pt->cap = w;
-                    }
+                    grow(pt, w);
                     d2d(c, pt->d, x + j * w, w);
                     pt->level = level;
                     pt->scale = in[v0 + g.second[j]].scale;
@@ -2385,7 +2415,8 @@ void dec_run(hec_context *ctx, const u64 *sk, const std::vector<DecEntry> &in, h
 
 void check_sk(const hec_context *ctx, const hec_secret_key *sk)
 {
-    need(sk && sk->ctx == ctx && sk->ctx_gen == ctx->gen && sk->d, "secret key is not valid for encryption parameters");
+    check_obj(ctx, sk, BAD_SK);
+    need(sk->d != nullptr, BAD_SK);
 }
 void check_dec_scale(const Ctx &c, double scale, std::size_t level)
 {
@@ -2399,50 +2430,24 @@ int hec_secret_key_upload(hec_context *ctx, const uint64_t *host, hec_secret_key
         need(ctx && host && out, "null argument");
         set_device(ctx);
         Ctx &c = ctx->c;
-        auto *k = new hec_secret_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
-        k->device = c.device;
+        auto k = make<hec_secret_key, hec_secret_key_destroy>(ctx);
         k->words = c.K * c.N;
         k->d = dalloc(k->words);
         HEC_HIP(hipMemcpyAsync(k->d, host, k->words * sizeof(u64), hipMemcpyHostToDevice, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
-        *out = k;
+        *out = k.release();
     });
 }
 int hec_secret_key_download(const hec_secret_key *sk, uint64_t *host)
 {
     return guard([&] {
         need(sk && host, "null argument");
-        need(ctx_alive(sk->ctx, sk->ctx_gen), "secret key is not valid for encryption parameters");
-        set_device(sk->ctx);
-        Ctx &c = sk->ctx->c;
+        Ctx &c = live(sk, BAD_SK);
         HEC_HIP(hipMemcpyAsync(host, sk->d, sk->words * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
     });
 }
-int hec_secret_key_destroy(hec_secret_key *sk)
-{
-    return guard([&] {
-        if (!sk) return;
-        // SEAL wipes a secret key's memory when it goes: zero-fill with the engine's fill kernel, on the context's
-        // stream while the context lives, else on the device's null stream (the key then touches nothing else)
-        (void)hipSetDevice(sk->device);
-        if (sk->d) {
-            const bool alive = ctx_alive(sk->ctx, sk->ctx_gen);
-            hipStream_t st = alive ? sk->ctx->c.stream : nullptr;
-            try {
-                Ctx wipe;
-                wipe.stream = st;
-                dev_fill32(wipe, sk->d, 0, sk->words * sizeof(u64));
-            } catch (...) {  // the memory is freed all the same
-            }
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(sk->d);
-        }
-        delete sk;
-    });
-}
+int hec_secret_key_destroy(hec_secret_key *sk) { return release(sk, sk ? sk->words : 0); }
 
 int hec_decrypt(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext *const *cts, uint64_t count,
                 hec_plaintext *const *out)
@@ -2456,8 +2461,7 @@ int hec_decrypt(hec_context *ctx, const hec_secret_key *sk, const hec_ciphertext
             check_ct(ctx, cts[i]);
             in[i] = {cts[i]->d, cts[i]->size, cts[i]->level, cts[i]->scale};
         }
-        for (u64 i = 0; i < count; ++i)
-            need(out[i] && out[i]->ctx == ctx, "plain is not valid for encryption parameters");
+        for (u64 i = 0; i < count; ++i) check_obj(ctx, out[i], BAD_PLAIN);
         if (count) dec_run(ctx, sk->d, in, out, 0, nullptr, nullptr);
     });
 }
@@ -2472,8 +2476,7 @@ int hec_decode(hec_context *ctx, const hec_plaintext *const *pts, uint64_t count
         std::vector<DecEntry> in(count);
         for (u64 i = 0; i < count; ++i) {
             const hec_plaintext *p = pts[i];
-            need(p && p->ctx == ctx && p->d && p->level >= 1 && p->level <= c.L,
-                 "plain is not valid for encryption parameters");
+            check_plain(ctx, p);
             in[i] = {p->d, 1, p->level, p->scale};
         }
         for (const DecEntry &e : in) check_dec_scale(c, e.scale, e.level);
@@ -2509,23 +2512,20 @@ int hec_kswitch_key_upload(hec_context *ctx, const uint64_t *host, hec_kswitch_k
     return guard([&] {
         need(ctx && host && out, "null argument");
         set_device(ctx);
-        auto *k = new hec_kswitch_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
+        auto k = make<hec_kswitch_key, hec_kswitch_key_destroy>(ctx);
         k->d = dalloc(key_words(ctx->c));
         // on the context stream, drained before the host buffer may go (a pageable hipMemcpy on the null stream is
         // not ordered with the non-blocking context stream)
         HEC_HIP(hipMemcpyAsync(k->d, host, key_words(ctx->c) * sizeof(u64), hipMemcpyHostToDevice, ctx->c.stream));
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
-        *out = k;
+        *out = k.release();
     });
 }
 int hec_kswitch_key_download(const hec_kswitch_key *key, uint64_t *host)
 {
     return guard([&] {
         need(key && host, "null argument");
-        set_device(key->ctx);
-        Ctx &c = key->ctx->c;
+        Ctx &c = live(key, BAD_RK);
         HEC_HIP(hipMemcpyAsync(host, key->d, key_words(c) * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
     });
@@ -2536,32 +2536,19 @@ int hec_kswitch_key_fill_uniform(hec_context *ctx, uint64_t seed, hec_kswitch_ke
         need(ctx && out, "null argument");
         set_device(ctx);
         Ctx &c = ctx->c;
-        auto *k = new hec_kswitch_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
+        auto k = make<hec_kswitch_key, hec_kswitch_key_destroy>(ctx);
         k->d = dalloc(key_words(c));
         fill_uniform(c, k->d, (int)(c.L * 2), (int)c.K, 0, 0, seed);
         HEC_HIP(hipStreamSynchronize(c.stream));
-        *out = k;
+        *out = k.release();
     });
 }
-int hec_kswitch_key_destroy(hec_kswitch_key *key)
-{
-    return guard([&] {
-        if (!key) return;
-        if (ctx_alive(key->ctx, key->ctx_gen)) (void)hipStreamSynchronize(key->ctx->c.stream);
-        (void)hipFree(key->d);
-        delete key;
-    });
-}
+int hec_kswitch_key_destroy(hec_kswitch_key *key) { return release(key); }
 int hec_galois_keys_create(hec_context *ctx, hec_galois_keys **out)
 {
     return guard([&] {
         need(ctx && out, "null argument");
-        auto *g = new hec_galois_keys();
-        g->ctx = ctx;
-        g->ctx_gen = ctx->gen;
-        *out = g;
+        *out = make<hec_galois_keys, hec_galois_keys_destroy>(ctx).release();
     });
 }
 static void gk_check_elt(const Ctx &c, u32 elt)
@@ -2572,8 +2559,7 @@ int hec_galois_keys_add(hec_galois_keys *gk, uint32_t elt, const uint64_t *host)
 {
     return guard([&] {
         need(gk && host, "null argument");
-        Ctx &c = gk->ctx->c;
-        set_device(gk->ctx);
+        Ctx &c = live(gk, BAD_GK);
         gk_check_elt(c, elt);
         HEC_HIP(hipStreamSynchronize(c.stream));  // a replaced key may still be read by enqueued work
         u64 *&d = gk->keys[elt];
@@ -2587,8 +2573,7 @@ int hec_galois_keys_download(const hec_galois_keys *gk, uint32_t elt, uint64_t *
 {
     return guard([&] {
         need(gk && host, "null argument");
-        set_device(gk->ctx);
-        Ctx &c = gk->ctx->c;
+        Ctx &c = live(gk, BAD_GK);
         const auto it = gk->keys.find(elt);
         need(it != gk->keys.end(), "Galois key not present");
         HEC_HIP(hipMemcpyAsync(host, it->second, key_words(c) * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
@@ -2599,8 +2584,7 @@ int hec_galois_keys_add_uniform(hec_galois_keys *gk, uint32_t elt, uint64_t seed
 {
     return guard([&] {
         need(gk != nullptr, "null argument");
-        Ctx &c = gk->ctx->c;
-        set_device(gk->ctx);
+        Ctx &c = live(gk, BAD_GK);
         gk_check_elt(c, elt);
         HEC_HIP(hipStreamSynchronize(c.stream));
         u64 *&d = gk->keys[elt];
@@ -2613,16 +2597,8 @@ int hec_galois_keys_add_uniform(hec_galois_keys *gk, uint32_t elt, uint64_t seed
 int hec_galois_keys_has(const hec_galois_keys *gk, uint32_t elt) { return gk && gk->keys.count(elt) ? 1 : 0; }
 int hec_galois_keys_destroy(hec_galois_keys *gk)
 {
-    return guard([&] {
-        if (!gk) return;
-        debug_key_tables_forget(gk);
-        if (ctx_alive(gk->ctx, gk->ctx_gen)) (void)hipStreamSynchronize(gk->ctx->c.stream);
-        for (auto &kv : gk->keys) (void)hipFree(kv.second);
-        for (auto &kv : gk->negw) (void)hipFree(kv.second);
-        for (auto &kv : gk->kw) (void)hipFree(kv.second);
-        for (auto &kv : gk->mkey) (void)hipFree(kv.second);
-        delete gk;
-    });
+    debug_key_tables_forget(gk);
+    return release(gk);
 }
 
 // ------------------------------------------------------------------ KeyGenerator / Encryptor
@@ -2829,15 +2805,6 @@ void rlwe_batch(Ctx &c, Scratch &s, HostKeep &keep, const u64 *sk, int nl, const
     s.top = top;
 }
 
-void check_pk(const hec_context *ctx, const hec_public_key *pk)
-{
-    need(pk && pk->ctx == ctx && pk->ctx_gen == ctx->gen && pk->d, "public key is not valid for encryption parameters");
-}
-void check_plain(const hec_context *ctx, const hec_plaintext *p)
-{
-    need(p && p->ctx == ctx && p->d && p->level >= 1 && p->level <= ctx->c.L,
-         "plain is not valid for encryption parameters");
-}
 static_assert(sizeof(RlweJob) % 8 == 0, "RlweJob is uploaded as words");
 
 // generate_one_kswitch_key for nkeys keys at once: key t's digit J is an RLWE sample over all K primes with
@@ -2867,22 +2834,14 @@ int hec_keygen_secret(hec_context *ctx, const uint64_t seed[8], hec_secret_key *
         set_device(ctx);
         Ctx &c = ctx->c;
         const Seed m = master_seed(seed);
-        auto *k = new hec_secret_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
-        k->device = c.device;
+        auto k = make<hec_secret_key, hec_secret_key_destroy>(ctx);
         k->words = c.K * c.N;
-        try {
-            k->d = fresh_words(c, k->words);
-            HostKeep keep;
-            Scratch s(c, ternary_words(c, 1));
-            sample_ternary(c, s, keep, {sub_seed(m, 1, 3, 0, 0)}, k->d, (int)c.K, true);
-            HEC_HIP(hipStreamSynchronize(c.stream));
-        } catch (...) {
-            (void)hec_secret_key_destroy(k);
-            throw;
-        }
-        *out = k;
+        k->d = fresh_words(c, k->words);
+        HostKeep keep;
+        Scratch s(c, ternary_words(c, 1));
+        sample_ternary(c, s, keep, {sub_seed(m, 1, 3, 0, 0)}, k->d, (int)c.K, true);
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        *out = k.release();
     });
 }
 
@@ -2894,21 +2853,14 @@ int hec_keygen_public(hec_context *ctx, const hec_secret_key *sk, const uint64_t
         check_sk(ctx, sk);
         Ctx &c = ctx->c;
         const Seed m = master_seed(seed);
-        auto *k = new hec_public_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
-        try {
-            k->d = fresh_words(c, 2 * c.K * c.N);
-            HostKeep keep;
-            Scratch s(c, rlwe_words(c, 1, c.K));
-            const RlweReq r{k->d, k->d + c.K * c.N, nullptr, 0, -1, sub_seed(m, 2, 1, 0, 0), sub_seed(m, 2, 2, 0, 0)};
-            rlwe_batch(c, s, keep, sk->d, (int)c.K, &r, 1);
-            HEC_HIP(hipStreamSynchronize(c.stream));
-        } catch (...) {
-            (void)hec_public_key_destroy(k);
-            throw;
-        }
-        *out = k;
+        auto k = make<hec_public_key, hec_public_key_destroy>(ctx);
+        k->d = fresh_words(c, 2 * c.K * c.N);
+        HostKeep keep;
+        Scratch s(c, rlwe_words(c, 1, c.K));
+        const RlweReq r{k->d, k->d + c.K * c.N, nullptr, 0, -1, sub_seed(m, 2, 1, 0, 0), sub_seed(m, 2, 2, 0, 0)};
+        rlwe_batch(c, s, keep, sk->d, (int)c.K, &r, 1);
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        *out = k.release();
     });
 }
 
@@ -2918,40 +2870,23 @@ int hec_public_key_upload(hec_context *ctx, const uint64_t *host, hec_public_key
         need(ctx && host && out, "null argument");
         set_device(ctx);
         Ctx &c = ctx->c;
-        auto *k = new hec_public_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
-        try {
-            k->d = dalloc(2 * c.K * c.N);
-            HEC_HIP(hipMemcpyAsync(k->d, host, 2 * c.K * c.N * sizeof(u64), hipMemcpyHostToDevice, c.stream));
-            HEC_HIP(hipStreamSynchronize(c.stream));
-        } catch (...) {
-            (void)hec_public_key_destroy(k);
-            throw;
-        }
-        *out = k;
+        auto k = make<hec_public_key, hec_public_key_destroy>(ctx);
+        k->d = dalloc(2 * c.K * c.N);
+        HEC_HIP(hipMemcpyAsync(k->d, host, 2 * c.K * c.N * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        *out = k.release();
     });
 }
 int hec_public_key_download(const hec_public_key *pk, uint64_t *host)
 {
     return guard([&] {
         need(pk && host, "null argument");
-        need(ctx_alive(pk->ctx, pk->ctx_gen), "public key is not valid for encryption parameters");
-        set_device(pk->ctx);
-        Ctx &c = pk->ctx->c;
+        Ctx &c = live(pk, BAD_PK);
         HEC_HIP(hipMemcpyAsync(host, pk->d, 2 * c.K * c.N * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
         HEC_HIP(hipStreamSynchronize(c.stream));
     });
 }
-int hec_public_key_destroy(hec_public_key *pk)
-{
-    return guard([&] {
-        if (!pk) return;
-        if (ctx_alive(pk->ctx, pk->ctx_gen)) (void)hipStreamSynchronize(pk->ctx->c.stream);
-        (void)hipFree(pk->d);
-        delete pk;
-    });
-}
+int hec_public_key_destroy(hec_public_key *pk) { return release(pk); }
 
 int hec_keygen_relin(hec_context *ctx, const hec_secret_key *sk, const uint64_t seed[8], hec_kswitch_key **out)
 {
@@ -2961,29 +2896,22 @@ int hec_keygen_relin(hec_context *ctx, const hec_secret_key *sk, const uint64_t 
         check_sk(ctx, sk);
         Ctx &c = ctx->c;
         const Seed m = master_seed(seed);
-        auto *k = new hec_kswitch_key();
-        k->ctx = ctx;
-        k->ctx_gen = ctx->gen;
-        try {
-            k->d = fresh_words(c, key_words(c));
-            HostKeep keep;
-            const std::size_t B = rlwe_chunk(c, c.L, c.K);
-            Scratch s(c, c.K * c.N + 64 + rlwe_words(c, B, c.K));
-            u64 *S2 = s.take(c.K * c.N);  // newkey = s (*) s
-            {
-                ProfScope ps(c, "k:k_dyadic", 3.0 * c.K);
-                ew_dyadic(c, sk->d, sk->d, S2, 0, (int)c.K, 1);
-            }
-            const u64 *nk = S2;
-            const u64 tag = 0;
-            kswitch_keygen(c, sk->d, m, 3, &k->d, &nk, &tag, 1, s, keep);
-            dev_zero(c, S2, c.K * c.N * sizeof(u64));  // a function of the secret key
-            HEC_HIP(hipStreamSynchronize(c.stream));
-        } catch (...) {
-            (void)hec_kswitch_key_destroy(k);
-            throw;
+        auto k = make<hec_kswitch_key, hec_kswitch_key_destroy>(ctx);
+        k->d = fresh_words(c, key_words(c));
+        HostKeep keep;
+        const std::size_t B = rlwe_chunk(c, c.L, c.K);
+        Scratch s(c, c.K * c.N + 64 + rlwe_words(c, B, c.K));
+        u64 *S2 = s.take(c.K * c.N);  // newkey = s (*) s
+        {
+            ProfScope ps(c, "k:k_dyadic", 3.0 * c.K);
+            ew_dyadic(c, sk->d, sk->d, S2, 0, (int)c.K, 1);
         }
-        *out = k;
+        const u64 *nk = S2;
+        const u64 tag = 0;
+        kswitch_keygen(c, sk->d, m, 3, &k->d, &nk, &tag, 1, s, keep);
+        dev_zero(c, S2, c.K * c.N * sizeof(u64));  // a function of the secret key
+        HEC_HIP(hipStreamSynchronize(c.stream));
+        *out = k.release();
     });
 }
 
@@ -2992,11 +2920,9 @@ int hec_keygen_galois(hec_galois_keys *gk, const hec_secret_key *sk, const uint3
 {
     return guard([&] {
         need(gk && (elts || n == 0), "null argument");
-        need(ctx_alive(gk->ctx, gk->ctx_gen), "null argument");
+        Ctx &c = live(gk, BAD_GK);
         hec_context *ctx = gk->ctx;
-        set_device(ctx);
         check_sk(ctx, sk);
-        Ctx &c = ctx->c;
         std::vector<u32> es(elts, elts + n);
         if (n == 0) {
             es.resize(hec_default_galois_elts(ctx, nullptr));
@@ -3046,8 +2972,7 @@ int hec_encrypt_symmetric(hec_context *ctx, const hec_secret_key *sk, const hec_
         check_sk(ctx, sk);
         Ctx &c = ctx->c;
         for (u64 v = 0; v < count; ++v) check_plain(ctx, pts[v]);
-        for (u64 v = 0; v < count; ++v)
-            need(out[v] && out[v]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        for (u64 v = 0; v < count; ++v) check_obj(ctx, out[v], BAD_CT);
         const Seed m = master_seed(seed);
         const u64 N = c.N;
         std::map<std::size_t, std::vector<u64>> groups;  // by level, as hec_decrypt groups
@@ -3062,7 +2987,7 @@ int hec_encrypt_symmetric(hec_context *ctx, const hec_secret_key *sk, const hec_
                 for (std::size_t b = 0; b < B; ++b) {
                     const u64 v = g.second[b0 + b];
                     hec_ciphertext *ct = out[v];
-                    ensure(ct, 2 * l * N);
+                    grow(ct, 2 * l * N);
                     req[b] = {ct->d, ct->d + l * N, pts[v]->d, 0, -1, sub_seed(m, 5, 1, v, 0), sub_seed(m, 5, 2, v, 0)};
                     if (public_seeds) std::memcpy(public_seeds + v * 8, req[b].a.data(), 64);
                 }
@@ -3088,8 +3013,7 @@ int hec_encrypt(hec_context *ctx, const hec_public_key *pk, const hec_plaintext 
         check_pk(ctx, pk);
         Ctx &c = ctx->c;
         for (u64 v = 0; v < count; ++v) check_plain(ctx, pts[v]);
-        for (u64 v = 0; v < count; ++v)
-            need(out[v] && out[v]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        for (u64 v = 0; v < count; ++v) check_obj(ctx, out[v], BAD_CT);
         const Seed m = master_seed(seed);
         const u64 N = c.N, K = c.K;
         std::map<std::size_t, std::vector<u64>> groups;
@@ -3115,7 +3039,7 @@ int hec_encrypt(hec_context *ctx, const hec_public_key *pk, const hec_plaintext 
                     su[b] = sub_seed(m, 6, 3, v, 0);
                     se[2 * b] = sub_seed(m, 6, 2, v, 0);
                     se[2 * b + 1] = sub_seed(m, 6, 2, v, 1);
-                    ensure(out[v], 2 * l * N);
+                    grow(out[v], 2 * l * N);
                     cts[b] = out[v]->d;
                     pp[b] = pts[v]->d;
                 }
@@ -3166,7 +3090,7 @@ int hec_ciphertext_load_seal(hec_ciphertext *ct, const void *bytes, uint64_t nby
 {
     return guard([&] {
         need(ct && bytes, "null argument");
-        Ctx &c = ct->ctx->c;
+        const Ctx &c = live(ct, BAD_CT);
         uint64_t size = 0, level = 0, N = 0, pid[4], used = 0;
         double scale = 0;
         // the context's data-level primes expand a seeded object (client.cpp:113-114 sends those)
@@ -3190,7 +3114,7 @@ int hec_ciphertext_save_seal(const hec_ciphertext *ct, int compr_mode, void *out
 {
     return guard([&] {
         need(ct && ct->d, "null argument");
-        const Ctx &c = ct->ctx->c;
+        const Ctx &c = live(ct, BAD_CT);
         std::vector<u64> host(ct->size * ct->level * c.N);
         const int rc = hec_ciphertext_download(ct, host.data());
         if (rc != HEC_OK) throw std::logic_error(hec_last_error());
@@ -3246,19 +3170,19 @@ int hec_galois_keys_load_seal_ex(hec_galois_keys *gk, const void *bytes, uint64_
 {
     return guard([&] {
         need(gk && bytes, "null argument");
-        need(gk->ctx, "null argument");
-        set_device(gk->ctx);
+        const Ctx &c = live(gk, BAD_GK);
         struct Visit {
             hec_galois_keys *gk;
+            const Ctx &c;
             uint64_t max_lists, seen = 0;
             std::string err;
             int rc = HEC_OK;
-        } v{gk, max_lists ? std::min<uint64_t>(max_lists, gk->ctx->c.N) : galois_lists_default(gk->ctx->c)};
+        } v{gk, c, max_lists ? std::min<uint64_t>(max_lists, c.N) : galois_lists_default(c)};
         // one pass over the object: GaloisKeys::get_index(elt) = (elt - 1) / 2, every non-empty list uploaded as it
         // is parsed
         auto cb = [](void *user, uint64_t index, const uint64_t *words, uint64_t nwords) -> int {
             auto *st = static_cast<Visit *>(user);
-            const Ctx &c = st->gk->ctx->c;
+            const Ctx &c = st->c;
             if (nwords != c.L * 2 * c.K * c.N) {
                 st->err = "galois_keys is not valid for encryption parameters";
                 return st->rc = HEC_EINVAL;
@@ -3272,7 +3196,7 @@ int hec_galois_keys_load_seal_ex(hec_galois_keys *gk, const void *bytes, uint64_
             return st->rc = rc;
         };
         uint64_t used = 0;
-        const int rc = hec_seal_kswitch_keys_foreach_ex(bytes, nbytes, seal_keys_max_bytes(gk->ctx->c, v.max_lists),
+        const int rc = hec_seal_kswitch_keys_foreach_ex(bytes, nbytes, seal_keys_max_bytes(c, v.max_lists),
                                                         cb, &v, nullptr, &used);
         if (v.rc != HEC_OK) {
             if (v.rc == HEC_EINVAL) throw std::invalid_argument(v.err);
@@ -3312,16 +3236,7 @@ static void add_sub(hec_context *ctx, hec_ciphertext *a, const hec_ciphertext *b
     Ctx &c = ctx->c;
     const u64 ps = a->level * c.N;
     const std::size_t mn = std::min(a->size, b->size), mx = std::max(a->size, b->size);
-    if (mx > a->size) {  // grow a, keeping its polys
-        if (a->cap < mx * ps) {
-            u64 *nd = dalloc(mx * ps);
-            d2d(c, nd, a->d, a->size * ps);
-            HEC_HIP(hipStreamSynchronize(c.stream));
-            HEC_HIP(hipFree(a->d));
-            a->d = nd;
-            a->cap = mx * ps;
-        }
-    }
+    grow(a, mx * ps, a->size * ps);  // keeping a's polys
     ew_add(c, PolyArr{a->d, 0, ps}, PolyArr{b->d, 0, ps}, PolyArr{a->d, 0, ps}, 1, (int)mn, (int)a->level,
            sub ? 1 : 0);
     if (b->size > a->size) {  // SEAL: copy (add) or negate (sub) the extra polys of b
@@ -3346,7 +3261,7 @@ int hec_sub_inplace(hec_context *ctx, hec_ciphertext *a, const hec_ciphertext *b
 static void plain_addsub(hec_context *ctx, hec_ciphertext *a, const hec_plaintext *p, bool sub)
 {
     check_ct(ctx, a);
-    need(p && p->ctx == ctx && p->d, "plain is not valid for encryption parameters");
+    check_plain_data(ctx, p);
     set_device(ctx);
     need(a->level == p->level, "encrypted and plain parameter mismatch");
     need(are_close(a->scale, p->scale), "scale mismatch");
@@ -3366,7 +3281,7 @@ int hec_multiply_plain_inplace(hec_context *ctx, hec_ciphertext *a, const hec_pl
 {
     return guard([&] {
         check_ct(ctx, a);
-        need(p && p->ctx == ctx && p->d, "plain is not valid for encryption parameters");
+        check_plain_data(ctx, p);
         set_device(ctx);
         need(a->level == p->level, "encrypted_ntt and plain_ntt parameter mismatch");
         const double ns = a->scale * p->scale;
@@ -3389,12 +3304,7 @@ static void multiply(hec_context *ctx, hec_ciphertext *a, const hec_ciphertext *
     Scratch s(c, ds * ps + 64);
     u64 *tmp = s.take(ds * ps);
     ct_multiply(c, a->d, (int)a->size, b->d, (int)b->size, tmp, (int)a->level);
-    if (a->cap < ds * ps) {
-        HEC_HIP(hipStreamSynchronize(c.stream));
-        HEC_HIP(hipFree(a->d));
-        a->d = dalloc(ds * ps);
-        a->cap = ds * ps;
-    }
+    grow(a, ds * ps);
     d2d(c, a->d, tmp, ds * ps);
     a->size = ds;
     a->scale = ns;
@@ -3412,7 +3322,7 @@ int hec_relinearize_inplace(hec_context *ctx, hec_ciphertext *a, const hec_kswit
 {
     return guard([&] {
         check_ct(ctx, a);
-        need(rk && rk->ctx == ctx, "relin_keys is not valid for encryption parameters");
+        check_obj(ctx, rk, BAD_RK);
         set_device(ctx);
         if (a->size == 2) return;
         need(a->size == 3, "not enough relinearization keys");
@@ -3472,7 +3382,7 @@ int hec_rotate_vector_inplace(hec_context *ctx, hec_ciphertext *a, int steps, co
 {
     return guard([&] {
         check_ct(ctx, a);
-        need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
+        check_obj(ctx, gk, BAD_GK);
         set_device(ctx);
         if (steps == 0) return;  // Evaluator::rotate_internal
         need(a->size == 2, "encrypted size must be 2");
@@ -3486,7 +3396,7 @@ int hec_apply_galois_inplace(hec_context *ctx, hec_ciphertext *a, uint32_t elt, 
 {
     return guard([&] {
         check_ct(ctx, a);
-        need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
+        check_obj(ctx, gk, BAD_GK);
         set_device(ctx);
         need(gk->keys.count(elt) > 0, "Galois key not present");
         gk_check_elt(ctx->c, elt);
@@ -3556,7 +3466,7 @@ int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, 
     return guard([&] {
         set_device(ctx);
         need(acc && out && p >= 1, "null argument");
-        need(rk && rk->ctx == ctx, "relin_keys is not valid for encryption parameters");
+        check_obj(ctx, rk, BAD_RK);
         Ctx &c = ctx->c;
         const std::size_t l = acc[0]->level, N = c.N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
         for (uint64_t i = 0; i < p; ++i) {
@@ -3573,7 +3483,7 @@ int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, 
         std::vector<double> sc(p);
         for (uint64_t i = 0; i < p; ++i) sc[i] = acc[i]->scale / (double)c.q[l - 1];
         for (uint64_t i = 0; i < p; ++i) {
-            ensure(out[i], So);
+            grow(out[i], So);
             d2d(c, out[i]->d, O + i * So, So);
             out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = sc[i];
         }
@@ -3609,7 +3519,7 @@ FftPlan FftPlan::make(hec_context *ctx, const hec_ciphertext *const *in, uint64_
     need(n >= 1 && !(n & (n - 1)), "n must be a power of two");
     for (uint64_t i = 0; i < count; ++i) {
         check_ct(ctx, in[i]);
-        need(out[i] && out[i]->ctx == ctx, "encrypted is not valid for encryption parameters");
+        check_obj(ctx, out[i], BAD_CT);
         need(in[i]->size == 2, "encrypted size must be 2");
         need(in[i]->level == in[0]->level, "encrypted1 and encrypted2 parameter mismatch");
         need(std::memcmp(&in[i]->scale, &in[0]->scale, sizeof(double)) == 0, "scale mismatch");
@@ -3684,7 +3594,7 @@ void fft_store(Ctx &c, const u64 *W, hec_ciphertext *const *out, std::size_t cnt
 {
     const std::size_t So = 2 * l * c.N;
     for (std::size_t i = 0; i < cnt; ++i) {
-        ensure(out[i], So);
+        grow(out[i], So);
         d2d(c, out[i]->d, W + i * So, So);
         out[i]->size = 2;
         out[i]->level = l;
@@ -3702,7 +3612,7 @@ int hec_fft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t n, int i
         const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
         if (p.total == 0) {  // n = 1 forward: copies
             if (out[0] != in[0]) {
-                ensure(out[0], S0);
+                grow(out[0], S0);
                 d2d(c, out[0]->d, in[0]->d, S0);
                 out[0]->size = 2; out[0]->level = l0; out[0]->scale = in[0]->scale;
             }
@@ -3774,13 +3684,13 @@ int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint
         set_device(ctx);
         need(n <= ctx->c.N / 2 || (n & (n - 1)), "n must be at most slot_count");
         const FftPlan p = FftPlan::make(ctx, in, B, n, inverse, out);
-        need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
+        check_obj(ctx, gk, BAD_GK);
         Ctx &c = ctx->c;
         const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
         if (p.total == 0) {
             for (uint64_t i = 0; i < B; ++i)
                 if (out[i] != in[i]) {
-                    ensure(out[i], S0);
+                    grow(out[i], S0);
                     d2d(c, out[i]->d, in[i]->d, S0);
                     out[i]->size = 2; out[i]->level = l0; out[i]->scale = in[i]->scale;
                 }
@@ -3967,7 +3877,7 @@ int hec_matmul_diag_col_sharded(hec_context *ctx, const hec_ciphertext *const *d
         std::string msg;
         try {
             need(diags && cols && out && n >= 1 && p >= 1, "empty matrix operand");
-            need(gk && gk->ctx == ctx, "galois_keys is not valid for encryption parameters");
+            check_obj(ctx, gk, BAD_GK);
             std::set<u32> keys;
             for (const auto &kv : gk->keys) keys.insert(kv.first);
             mine = plan_shards(c.N, n, ctx->world, keys)[ctx->rank];
@@ -3984,7 +3894,7 @@ int hec_matmul_diag_col_sharded(hec_context *ctx, const hec_ciphertext *const *d
         // this rank's size-3 partials over its trie subtrees of diagonals
         std::vector<hec_ciphertext> acc(p);
         std::vector<hec_ciphertext *> accp(p);
-        for (uint64_t i = 0; i < p; ++i) { acc[i].ctx = ctx; acc[i].ctx_gen = ctx->gen; accp[i] = &acc[i]; }
+        for (uint64_t i = 0; i < p; ++i) { bind(acc[i], ctx); accp[i] = &acc[i]; }
         struct Free {
             std::vector<hec_ciphertext> &a;
             ~Free() { for (auto &x : a) if (x.d) (void)hipFree(x.d); }
@@ -4015,7 +3925,8 @@ int hec_matmul_col_colT(hec_context *ctx, const hec_ciphertext *const *A, uint64
     return guard([&] {
         set_device(ctx);
         need(A && B && out && n >= 1 && p >= 1, "null argument");
-        need(rk && rk->ctx == ctx && gk && gk->ctx == ctx, "keys are not valid for encryption parameters");
+        check_obj(ctx, rk, "keys are not valid for encryption parameters");
+        check_obj(ctx, gk, "keys are not valid for encryption parameters");
         Ctx &c = ctx->c;
         const std::size_t l = A[0]->level, N = c.N, S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
         for (uint64_t j = 0; j < n; ++j) {
@@ -4060,7 +3971,7 @@ int hec_matmul_col_colT(hec_context *ctx, const hec_ciphertext *const *A, uint64
         keyswitch(c, s, PolyArr{AC + 2 * l * N, S3, 0}, rk->d, Ca, 2, Ca, (int)p, (int)l);
         rescale_batch(c, s, Ca, (int)p, 2, (int)l, PolyArr{O, So, (l - 1) * N});
         for (uint64_t i = 0; i < p; ++i) {
-            ensure(out[i], So);
+            grow(out[i], So);
             d2d(c, out[i]->d, O + i * So, So);
             out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = sc / (double)c.q[l - 1];
         }
@@ -4074,7 +3985,7 @@ int hec_matrix_matmul(hec_context *ctx, const hec_ciphertext *const *A, uint64_t
     return guard([&] {
         set_device(ctx);
         need(A && B && out, "null argument");
-        need(rk && rk->ctx == ctx, "relin_keys is not valid for encryption parameters");
+        check_obj(ctx, rk, BAD_RK);
         Ctx &c = ctx->c;
         // Matrix::get_dims / ij_to_idx (he_linalg.cpp:25-28, 376-379)
         const uint64_t r1 = atr ? ac : ar, c1 = atr ? ar : ac, r2 = btr ? bc : br, c2 = btr ? br : bc;
@@ -4120,7 +4031,7 @@ int hec_matrix_matmul(hec_context *ctx, const hec_ciphertext *const *A, uint64_t
         keyswitch(c, s, PolyArr{AC + 2 * l * N, S3, 0}, rk->d, Ca, 2, Ca, (int)no, (int)l);
         rescale_batch(c, s, Ca, (int)no, 2, (int)l, PolyArr{O, So, (l - 1) * N});
         for (uint64_t o = 0; o < no; ++o) {
-            ensure(out[o], So);
+            grow(out[o], So);
             d2d(c, out[o]->d, O + o * So, So);
             out[o]->size = 2; out[o]->level = l - 1; out[o]->scale = sc[o] / (double)c.q[l - 1];
         }

@@ -59,7 +59,11 @@ int hec_context_create(uint64_t poly_modulus_degree, const uint64_t *coeff_modul
                        hec_context **out);
 /* Objects (ciphertexts, plaintexts, keys) may be destroyed before or after their context, in any order, as SEAL's
  * objects holding their context by shared_ptr allow: an object destroyed after its context frees its own device
- * memory and touches nothing else. */
+ * memory and touches nothing else.  The destroys (of objects and of contexts) may run on any thread, concurrently
+ * with each other, as a garbage collector's finalisers do; every other call on a context and its objects comes from
+ * one host thread at a time.  A call on an object whose context is gone fails with HEC_EINVAL and the object kind's
+ * "... is not valid for encryption parameters" message.  A handle is never valid for a later context, even one
+ * created at the destroyed context's address: such a call fails the same way. */
 int hec_context_destroy(hec_context *ctx);
 int hec_context_set_stream(hec_context *ctx, void *hip_stream); /* NULL = context-owned stream */
 int hec_context_synchronize(hec_context *ctx);

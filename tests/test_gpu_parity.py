@@ -175,8 +175,14 @@ def test_objects_outlive_their_context(orc, hecdna):
         rk = ctx.relin_key(seed=11)
         o = orc.Oracle(N, m)
         gk = ctx.galois_keys(uniform_elts=[o.elt_from_step(1)], seed=5)
+        # the kinds made on the device: a secret key, a public key, a generated relin key and Galois key set
+        seed = bytes(range(64))
+        sk = ctx.keygen_secret(seed)
+        pk = ctx.keygen_public(sk, seed)
+        grk = ctx.keygen_relin(sk, seed)
+        ggk = ctx.keygen_galois(sk, [o.elt_from_step(1)], seed)
         ctx.close()
-        del ct, pt, rk, gk
+        del ct, pt, rk, gk, sk, pk, grk, ggk
         gc.collect()
     ctx = hecdna.Context(N, m)
     a = np.stack([np.stack([np.random.default_rng(9).integers(0, q, N, dtype=np.uint64) for q in m])])
