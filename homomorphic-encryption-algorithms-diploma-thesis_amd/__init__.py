@@ -169,6 +169,13 @@ def lib():
             "hec_decrypt_decode": [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)],
             "hec_bfft": [vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp],
+            "hec_math_plan": [u64p, C.c_uint64, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_double, u64p,
+                              C.POINTER(C.c_double)],
+            "hec_math_signed_inv": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
+            "hec_math_inv_sqrt_twice": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
+            "hec_math_sqrt": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
+            "hec_math_abs": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
+            "hec_drop_chain_levels": [vp, vp, C.c_uint64, C.c_uint64],
             "hec_keygen_secret": [vp, u64p, C.POINTER(vp)],
             "hec_keygen_public": [vp, vp, u64p, C.POINTER(vp)],
             "hec_public_key_upload": [vp, u64p, C.POINTER(vp)],
@@ -460,6 +467,20 @@ def bfft_diagonal(d, k, n, inverse=False) -> np.ndarray:
                                im.ctypes.data_as(dp)) != 0:
         raise InvalidArgument(1, "bfft_diagonal: d in {0, 1, 2} (d = 2 needs k > 2), k <= n powers of two")
     return np.array([complex(a, b) for a, b in zip(re, im)])
+
+
+MATH_SIGNED_INV, MATH_INV_SQRT_TWICE, MATH_SQRT, MATH_ABS = 0, 1, 2, 3
+
+
+def math_plan(moduli, fn, a, iters, level, scale):
+    """hec_math_plan (host only): the (level, scale) that Context.signed_inv / inv_sqrt_twice / sqrt / abs (fn =
+    MATH_*) return for inputs at (level, scale) on the key moduli `moduli`; raises InvalidArgument with the message of
+    the first check the per-operation schedule would fail."""
+    m = np.array([int(x) for x in moduli], dtype=np.uint64)
+    lv, sc = C.c_uint64(), C.c_double()
+    _check(lib().hec_math_plan(_p(m), len(m), int(fn), float(a), int(iters), int(level), float(scale), C.byref(lv),
+                               C.byref(sc)))
+    return lv.value, sc.value
 
 
 def create_coeff_modulus(N, bits):
@@ -782,6 +803,41 @@ class Context:
         out = out or [Ciphertext(self) for _ in cts]
         _check(lib().hec_bfft(self.h, self._arr(cts), len(cts), int(n), int(bool(inverse)), gk.h, self._arr(out)))
         return out[0] if single else out
+
+    # -------------------------------------------------------------- he::math
+    def _math(self, fn, cts, a, iters, rk, out):
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        if out is None:
+            out = [Ciphertext(self) for _ in cts]
+        elif isinstance(out, Ciphertext):
+            out = [out]
+        _check(fn(self.h, self._arr(cts), len(cts), float(a), int(iters), rk.h, self._arr(out)))
+        return out[0] if single else out
+
+    def signed_inv(self, cts, a, iters, rk, out=None):
+        """hec_math_signed_inv: he::math::signed_inv on every ciphertext of the list (or on one, then one is
+        returned), 1 / x from the guess a with |a x - 1| < 1."""
+        return self._math(lib().hec_math_signed_inv, cts, a, iters, rk, out)
+
+    def inv_sqrt_twice(self, cts, a, iters, rk, out=None):
+        """hec_math_inv_sqrt_twice: he::math::inv_sqrt_twice, 1 / sqrt(2 x) from the guess a."""
+        return self._math(lib().hec_math_inv_sqrt_twice, cts, a, iters, rk, out)
+
+    def sqrt(self, cts, a, iters, rk, out=None):
+        """hec_math_sqrt: he::math::sqrt."""
+        return self._math(lib().hec_math_sqrt, cts, a, iters, rk, out)
+
+    def abs(self, cts, a, iters, rk, out=None):
+        """hec_math_abs: he::math::abs."""
+        return self._math(lib().hec_math_abs, cts, a, iters, rk, out)
+
+    def drop_chain_levels(self, cts, levels):
+        """hec_drop_chain_levels: he::util::drop_chain_levels on the ciphertext(s), in place."""
+        single = isinstance(cts, Ciphertext)
+        lst = [cts] if single else list(cts)
+        _check(lib().hec_drop_chain_levels(self.h, self._arr(lst), len(lst), int(levels)))
+        return cts
 
     def reduce(self, ct):
         """Reduce every word of ct mod its prime (after a partial-sum exchange)."""

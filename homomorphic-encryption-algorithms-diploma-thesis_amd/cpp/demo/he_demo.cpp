@@ -18,6 +18,9 @@
 //                          matrix_operations.cpp:1106-1108; written as size-1 entries)
 //          math:<iter>    (he::math on the he_math.h drop-in: signed_inv(c0, 1.0), inv_sqrt_twice(c0, 0.7),
 //                          sqrt(c0, 1.0), abs(c1, 1.0) with <iter> iterations, src/core/he_math.cpp:22-269)
+//          mathb:<iter>   (the same four functions through he_math.h's vector overloads, each on all n input
+//                          ciphertexts as one batch: signed_inv(., 1.0), inv_sqrt_twice(., 0.7), sqrt(., 1.0),
+//                          abs(., 1.0); 4 n outputs in that order)
 //          util           (he::util: drop_chain_levels(c0, 2), then reach_chain_level of {c1, c2} to c0's level,
 //                          include/he_util.h:27-77; the chain indices of every output are printed)
 //          least_squares  (src/demos/matrix_operations.cpp:915-1003 on x = c0, y = c1 of 5 data slots: the sums,
@@ -228,7 +231,7 @@ int selfcontained(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
     if (argc != 4) {
-        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|"
+        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|mathb:<iter>|"
                      "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|selfcontained|server> <in.bin> <out.bin>\n";
         return 1;
     }
@@ -354,6 +357,14 @@ int main(int argc, char **argv)
         keep.push_back(he::math::inv_sqrt_twice(cencd, eval, rk, cts[0], 0.7, iter));
         keep.push_back(he::math::sqrt(ctx, cencd, eval, rk, cts[0], 1.0, iter));
         keep.push_back(he::math::abs(ctx, cencd, eval, rk, cts[1], 1.0, iter));
+    } else if (mode.rfind("mathb:", 0) == 0) {
+        // the vector overloads of he_math.h (an extension over the reference): every input ciphertext in one batch
+        const std::size_t iter = std::stoul(mode.substr(6));
+        hecdna::CKKSEncoder cencd(ctx);
+        for (auto &c : he::math::signed_inv(cencd, eval, rk, cts, 1.0, iter)) keep.push_back(std::move(c));
+        for (auto &c : he::math::inv_sqrt_twice(cencd, eval, rk, cts, 0.7, iter)) keep.push_back(std::move(c));
+        for (auto &c : he::math::sqrt(ctx, cencd, eval, rk, cts, 1.0, iter)) keep.push_back(std::move(c));
+        for (auto &c : he::math::abs(ctx, cencd, eval, rk, cts, 1.0, iter)) keep.push_back(std::move(c));
     } else if (mode.rfind("fft:", 0) == 0 || mode.rfind("bfft:", 0) == 0) {
         const bool slot = mode[0] == 'b';
         const std::string arg = mode.substr(slot ? 5 : 4);

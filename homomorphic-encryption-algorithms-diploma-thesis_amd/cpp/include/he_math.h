@@ -4,6 +4,8 @@
 // scalar encodes, plaintext and ciphertext products, relinearizations and rescales (src/core/he_math.cpp:22-269),
 // so on the same inputs and keys every intermediate ciphertext equals SEAL's bit for bit.
 #include <cstddef>
+#include <cstdint>
+#include <vector>
 
 #include "he_operators.h"
 #include "hecdna/seal_compat.hpp"
@@ -25,4 +27,59 @@ namespace he::math
     // f(x) = |x| (he_math.h:30-33)
     hecdna::Ciphertext abs(const hecdna::Context &ctx, const hecdna::CKKSEncoder &cencd, const hecdna::Evaluator &eval,
                            const hecdna::RelinKeys &rk, const hecdna::Ciphertext &x_ct, double a, std::size_t iter_num);
+
+    // An extension (the reference has no such overloads): the same four functions on a vector of ciphertexts of one
+    // level and scale, each one engine call (hec_math_*, include/hecdna.h) that runs every stage of the schedule
+    // above over the whole batch.  Result i equals the single-ciphertext function on x_cts[i], bit for bit.  The
+    // encoder argument is kept for the signature: the engine forms the scalar constants itself.
+    namespace detail
+    {
+        using batch_fn = int (*)(hec_context *, const hec_ciphertext *const *, std::uint64_t, double, std::uint64_t,
+                                 const hec_kswitch_key *, hec_ciphertext *const *);
+        inline std::vector<hecdna::Ciphertext> run(batch_fn fn, const hecdna::Evaluator &eval, const hecdna::RelinKeys &rk,
+                                                   const std::vector<hecdna::Ciphertext> &x_cts, double a,
+                                                   std::size_t iter_num)
+        {
+            const hecdna::Context &ctx = eval.context();
+            std::vector<hecdna::Ciphertext> res(x_cts.size());
+            std::vector<const hec_ciphertext *> in(x_cts.size());
+            std::vector<hec_ciphertext *> out(x_cts.size());
+            for (std::size_t i = 0; i < x_cts.size(); ++i) {
+                res[i].bind(ctx);
+                in[i] = x_cts[i].get();
+                out[i] = res[i].get();
+            }
+            hecdna::check(fn(ctx.get(), in.data(), in.size(), a, iter_num, rk.get(), out.data()));
+            return res;
+        }
+    } // namespace detail
+
+    inline std::vector<hecdna::Ciphertext> signed_inv(const hecdna::CKKSEncoder &, const hecdna::Evaluator &eval,
+                                                      const hecdna::RelinKeys &rk,
+                                                      const std::vector<hecdna::Ciphertext> &x_cts, double a,
+                                                      std::size_t iter_num)
+    {
+        return detail::run(hec_math_signed_inv, eval, rk, x_cts, a, iter_num);
+    }
+    inline std::vector<hecdna::Ciphertext> inv_sqrt_twice(const hecdna::CKKSEncoder &, const hecdna::Evaluator &eval,
+                                                          const hecdna::RelinKeys &rk,
+                                                          const std::vector<hecdna::Ciphertext> &x_cts, double a,
+                                                          std::size_t iter_num)
+    {
+        return detail::run(hec_math_inv_sqrt_twice, eval, rk, x_cts, a, iter_num);
+    }
+    inline std::vector<hecdna::Ciphertext> sqrt(const hecdna::Context &, const hecdna::CKKSEncoder &,
+                                                const hecdna::Evaluator &eval, const hecdna::RelinKeys &rk,
+                                                const std::vector<hecdna::Ciphertext> &x_cts, double a,
+                                                std::size_t iter_num)
+    {
+        return detail::run(hec_math_sqrt, eval, rk, x_cts, a, iter_num);
+    }
+    inline std::vector<hecdna::Ciphertext> abs(const hecdna::Context &, const hecdna::CKKSEncoder &,
+                                               const hecdna::Evaluator &eval, const hecdna::RelinKeys &rk,
+                                               const std::vector<hecdna::Ciphertext> &x_cts, double a,
+                                               std::size_t iter_num)
+    {
+        return detail::run(hec_math_abs, eval, rk, x_cts, a, iter_num);
+    }
 } // namespace he::math

@@ -1885,6 +1885,7 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "tensor_bufs") c.tensor_defer_bufs = (int)std::max<int64_t>(1, value);
             else if (n == "tensor_xcd") c.tensor_xcd = (int)std::max<int64_t>(0, value);
             else if (n == "prng_group") c.prng_group = in(0, 16);
+            else if (n == "math_chunk") c.math_chunk = in(0, 65535);
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -2210,9 +2211,30 @@ static u64 exact_residue(double a, u64 q)
     return r;
 }
 
+// The data primes of a modulus chain on the host: what the scalar encoder and the scale checks need, with or without a
+// device context (hec_math_plan has none)
+struct Chain {
+    const u64 *q = nullptr;
+    std::size_t L = 0;
+    int total_bits(std::size_t level) const
+    {
+        int b = 0;
+        for (std::size_t i = 0; i < level; ++i) b += 64 - __builtin_clzll(q[i]);
+        return b;
+    }
+    bool scale_ok(double scale, std::size_t level) const  // SEAL is_scale_within_bounds
+    {
+        return !(scale <= 0 || (int)std::log2(scale) >= total_bits(level));
+    }
+};
 // SEAL 4.1 CKKSEncoder::encode_internal(double value, parms_id, scale, destination) up to its fill: the checks, in its
 // order, and the word of every limb
+static void scalar_words_chain(const Chain &c, double value, double scale, std::size_t level, u64 *words);
 static void scalar_words(const Ctx &c, double value, double scale, std::size_t level, u64 *words)
+{
+    scalar_words_chain(Chain{c.q.data(), c.L}, value, scale, level, words);
+}
+static void scalar_words_chain(const Chain &c, double value, double scale, std::size_t level, u64 *words)
 {
     if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
     const int total = c.total_bits(level);
@@ -3768,6 +3790,363 @@ int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint
         }
         HEC_HIP(hipStreamSynchronize(c.stream));  // the host diagonals go out of scope
     });
+}
+
+// ------------------------------------------------------------------ he::math ---------------
+// signed_inv / inv_sqrt_twice / sqrt / abs (reference src/core/he_math.cpp:22-269) and he::util::drop_chain_levels on
+// a batch of ciphertexts of one level and scale.  Each schedule is written once, over MathRun, whose operations do the
+// host bookkeeping of the per-operation sequence (every scalar encode's checks, every product scale and its bound,
+// every division by q, every are_close, the end of the chain) in that sequence's order, and, when the run has a
+// device side, launch the stage over the whole batch.  A call walks its schedule twice: first without a device side
+// (the plan: the first failing check is the call's error, nothing has been written, and the peak number of live
+// iterates is known), then on the device.  hec_math_plan is the first walk alone.
+// Two stage kinds (hec_kernels.hip): the scalar stage OUT = rescale(A (*) c) +- d (math_lastprod, the batched INTT,
+// fft_round_limbs, math_cstage) and the product stage OUT = rescale(relin(A (*) (B' + d))) (math_tensor, then
+// keyswitch and rescale_batch as hec_matmul_finish runs them).  The iterates live in slots of one Scratch workspace.
+namespace {
+constexpr int MATH_MAX_JOBS = 65535;  // blocks along y of one NTT pass
+constexpr std::size_t MATH_AUTO_CHUNK = 256;  // automatic ciphertexts per pass at most (workspace size)
+
+struct MathVal {
+    int slot = -1;
+    std::size_t level = 0;
+    double scale = 0;
+};
+
+struct MathRun {
+    Chain ch;
+    // device side; c == nullptr is the planning walk
+    Ctx *c = nullptr;
+    Scratch *s = nullptr;
+    const u64 *rk = nullptr;
+    int B = 0;
+    std::vector<u64 *> slot;
+    u64 *T3 = nullptr, *Y = nullptr, *Z = nullptr;
+    // slot bookkeeping, the same on both walks
+    std::vector<char> busy;
+    int peak = 0;
+
+    int take()
+    {
+        std::size_t i = 0;
+        while (i < busy.size() && busy[i]) ++i;
+        if (i == busy.size()) busy.push_back(0);
+        busy[i] = 1;
+        peak = std::max(peak, (int)i + 1);
+        return (int)i;
+    }
+    void drop(MathVal &v)
+    {
+        if (v.slot >= 0) busy[(std::size_t)v.slot] = 0;
+        v.slot = -1;
+    }
+    PolyArr arr(const MathVal &v) const
+    {
+        return PolyArr{slot[(std::size_t)v.slot], 2 * v.level * c->N, v.level * c->N};
+    }
+
+    // rescale(a (*) encode(cval, a.level, pscale)) [+- encode(dval) at the result's level and scale]: multiply_plain,
+    // rescale_to_next, add_plain / sub_plain.  dmode 0 none, 1 add, 2 subtract; pscale 0: a's own scale
+    MathVal cstage(const MathVal &a, double cval, int dmode = 0, double dval = 0, double pscale = 0)
+    {
+        const std::size_t l = a.level;
+        u64 cw[HEC_MAXL + 1], dw[HEC_MAXL + 1];
+        if (pscale == 0) pscale = a.scale;
+        scalar_words_chain(ch, cval, pscale, l, cw);
+        const double ns = a.scale * pscale;
+        need(ch.scale_ok(ns, l), "scale out of bounds");
+        if (l == 1) throw std::invalid_argument("end of modulus switching chain reached");
+        MathVal o;
+        o.level = l - 1;
+        o.scale = ns / (double)ch.q[l - 1];
+        if (dmode) {
+            scalar_words_chain(ch, dval, o.scale, o.level, dw);
+            need(are_close(o.scale, o.scale), "scale mismatch");  // add_plain's check; the plaintext has o's scale
+            if (dmode == 2)
+                for (std::size_t i = 0; i < o.level; ++i) dw[i] = dw[i] ? ch.q[i] - dw[i] : 0;
+        }
+        o.slot = take();
+        if (c) {
+            const u64 N = c->N, sb = 2 * l * N, sk = l * N;
+            const u64 *A = slot[(std::size_t)a.slot];
+            {
+                ProfScope k(*c, "k:k_math_lastprod/math", 4.0 * B);
+                math_lastprod(*c, A, sb, sk, Y, B, 2, (int)l, cw[l - 1]);
+            }
+            {
+                ProfScope k(*c, "k:k_ntt/math_intt", 8.0 * B, 2);
+                const int pm[1] = {(int)l - 1};
+                ntt_strided(*c, true, Y, N, Y, N, 1, pm, 2 * B);
+            }
+            {
+                ProfScope k(*c, "k:k_ntt/math_round_a", 2.0 * B * l);
+                fft_round_limbs(*c, Y, Z, B, 2, (int)l);
+            }
+            {  // Z, the source's data limbs and the outputs, once each
+                ProfScope k(*c, "k:k_ntt/math_cstage", 6.0 * B * (l - 1));
+                math_cstage(*c, Z, A, sb, sk, arr(o), B, 2, (int)l, cw, dmode ? dw : nullptr);
+            }
+        }
+        return o;
+    }
+
+    // rescale(relin(a (*) (b [+ encode(dval, b.level, b.scale)]))): add_plain, multiply / square, relinearize,
+    // rescale_to_next.  a and b may be one value (the square)
+    MathVal prod(const MathVal &a, const MathVal &b, bool has_d = false, double dval = 0)
+    {
+        u64 dw[HEC_MAXL + 1];
+        if (has_d) {
+            scalar_words_chain(ch, dval, b.scale, b.level, dw);
+            need(are_close(b.scale, b.scale), "scale mismatch");  // add_plain's check; the plaintext has b's scale
+        }
+        need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
+        const std::size_t l = a.level;
+        const double ns = a.scale * b.scale;
+        need(ch.scale_ok(ns, l), "scale out of bounds");
+        if (l == 1) throw std::invalid_argument("end of modulus switching chain reached");
+        MathVal o;
+        o.level = l - 1;
+        o.scale = ns / (double)ch.q[l - 1];
+        o.slot = take();
+        if (c) {
+            const u64 N = c->N, S3 = 3 * l * N;
+            const bool same = a.slot == b.slot;
+            {
+                ProfScope k(*c, "k:k_math_tensor/math", ((same ? 2.0 : 4.0) + 3.0) * B * l);
+                math_tensor(*c, arr(a), arr(b), has_d ? dw : nullptr, T3, B, (int)l);
+            }
+            const PolyArr Aa{T3, S3, l * N};
+            keyswitch(*c, *s, PolyArr{T3 + 2 * l * N, S3, 0}, rk, Aa, 2, Aa, B, (int)l);
+            rescale_batch(*c, *s, Aa, B, 2, (int)l, arr(o));
+        }
+        return o;
+    }
+
+    // a - b into a's slot (sub_inplace)
+    void sub(MathVal &a, const MathVal &b)
+    {
+        need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
+        need(are_close(a.scale, b.scale), "scale mismatch");
+        if (c) ew_add(*c, arr(a), arr(b), arr(a), B, 2, (int)a.level, 1);
+    }
+
+    // he_math.cpp:22-90
+    MathVal signed_inv(const MathVal &x, double a, std::size_t iters)
+    {
+        MathVal y = cstage(x, -a * a, 1, 2 * a);
+        if (iters == 1) return y;
+        MathVal e = cstage(x, a, 2, 1.0);
+        MathVal t = cstage(y, 1.0, 0, 0, e.scale);  // y drops one level with the plaintext 1 encoded for e
+        drop(y);
+        y = t;
+        for (std::size_t i = 1; i < iters; ++i) {
+            t = prod(e, e);
+            drop(e);
+            e = t;
+            t = prod(y, e, true, 1.0);  // y (e^2 + 1)
+            drop(y);
+            y = t;
+        }
+        drop(e);
+        return y;
+    }
+
+    // he_math.cpp:95-164 (the `#if 1` form)
+    MathVal inv_sqrt_twice(const MathVal &x, double a, std::size_t iters)
+    {
+        const double y0 = a;
+        MathVal xl = x;  // x, dropped alongside the iterate; the caller's value is never released here
+        bool own = false;
+        MathVal y = cstage(x, -y0 * y0 * y0, 1, 3.0 / 2 * y0);
+        for (std::size_t i = 1; i < iters; ++i) {
+            MathVal yp = y;
+            MathVal t = cstage(yp, 3.0 / 2);
+            y = cstage(t, 1.0);
+            drop(t);
+            for (std::size_t j = 0; j < (i > 1 ? 2u : 1u); ++j) {
+                t = cstage(xl, 1.0);
+                if (own) drop(xl);
+                xl = t;
+                own = true;
+            }
+            MathVal xy = prod(xl, yp);
+            t = prod(yp, yp);
+            drop(yp);
+            yp = prod(t, xy);
+            drop(t);
+            drop(xy);
+            sub(y, yp);
+            drop(yp);
+        }
+        if (own) drop(xl);
+        return y;
+    }
+
+    // he_math.cpp:211-232; the level difference in size_t, as he::util::reach_chain_level takes it
+    MathVal sqrt(const MathVal &x, double a, std::size_t iters)
+    {
+        MathVal y = inv_sqrt_twice(x, 1 / a / std::sqrt(2), iters);
+        MathVal sv = cstage(x, std::sqrt(2));
+        const std::size_t n = (sv.level - 1) - (y.level - 1);
+        for (std::size_t k = 0; k < n; ++k) {
+            MathVal t = cstage(sv, 1.0);
+            drop(sv);
+            sv = t;
+        }
+        MathVal o = prod(y, sv);
+        drop(y);
+        drop(sv);
+        return o;
+    }
+
+    // he_math.cpp:237-269
+    MathVal abs(const MathVal &x, double a, std::size_t iters)
+    {
+        MathVal sq = prod(x, x);
+        MathVal y = inv_sqrt_twice(sq, 1 / a / std::sqrt(2), iters);
+        MathVal t = cstage(sq, std::sqrt(2));
+        drop(sq);
+        sq = t;
+        const std::size_t n = (sq.level - 1) - (y.level - 1);
+        for (std::size_t k = 0; k < n; ++k) {
+            t = cstage(sq, 1.0);
+            drop(sq);
+            sq = t;
+        }
+        MathVal o = prod(y, sq);
+        drop(y);
+        drop(sq);
+        return o;
+    }
+
+    // he_util.h:27-48
+    MathVal drop_levels(const MathVal &x, std::size_t levels)
+    {
+        MathVal v = x;
+        for (std::size_t k = 0; k < levels; ++k) {
+            MathVal t = cstage(v, 1.0);
+            if (k) drop(v);
+            v = t;
+        }
+        return v;
+    }
+
+    // fn: HEC_MATH_*, or -1 for drop_levels with iters levels.  The input occupies slot 0
+    MathVal run(int fn, double a, std::size_t iters, std::size_t level, double scale)
+    {
+        busy.assign(1, 1);
+        peak = 1;
+        MathVal x;
+        x.slot = 0;
+        x.level = level;
+        x.scale = scale;
+        switch (fn) {
+        case -1: return drop_levels(x, iters);
+        case HEC_MATH_SIGNED_INV: return signed_inv(x, a, iters);
+        case HEC_MATH_INV_SQRT_TWICE: return inv_sqrt_twice(x, a, iters);
+        case HEC_MATH_SQRT: return sqrt(x, a, iters);
+        case HEC_MATH_ABS: return abs(x, a, iters);
+        default: throw std::invalid_argument("unknown he::math function");
+        }
+    }
+};
+
+void math_batch(hec_context *ctx, int fn, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iters,
+                const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    need(ctx && x && out && B >= 1, "null argument");
+    set_device(ctx);
+    for (uint64_t i = 0; i < B; ++i) {
+        check_ct(ctx, x[i]);
+        check_obj(ctx, out[i], BAD_CT);
+        need(x[i]->size == 2, "encrypted size must be 2");
+        need(x[i]->level == x[0]->level, "encrypted1 and encrypted2 parameter mismatch");
+        need(std::memcmp(&x[i]->scale, &x[0]->scale, sizeof(double)) == 0, "scale mismatch");
+    }
+    if (fn >= 0) {
+        need(iters >= 1, "iter_num must be positive");
+        check_obj(ctx, rk, BAD_RK);
+    }
+    Ctx &c = ctx->c;
+    const std::size_t N = c.N, l0 = x[0]->level, S0 = 2 * l0 * N;
+    MathRun plan;
+    plan.ch = Chain{c.q.data(), c.L};
+    const MathVal res = plan.run(fn, a, iters, l0, x[0]->scale);
+    if (res.slot == 0) return;  // no level to drop: the inputs are the results
+    // ciphertexts per pass: the key switch's mod-up pass B runs Bc l0 l0 blocks along y
+    std::size_t Bc = std::min<std::size_t>(MATH_AUTO_CHUNK, std::max<std::size_t>(1, MATH_MAX_JOBS / ((l0 + 1) * l0)));
+    if (c.math_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.math_chunk);
+    Bc = std::min<std::size_t>(Bc, B);
+    const std::size_t nslot = (std::size_t)plan.peak;
+    Scratch s(c, nslot * Bc * S0 + Bc * 3 * l0 * N + 2 * Bc * N + 2 * Bc * l0 * N + ks_words(c, Bc, l0) +
+                     rescale_words(c, Bc, 2, l0) + (nslot + 16) * 64);
+    MathRun dev;
+    dev.ch = plan.ch;
+    dev.c = &c;
+    dev.s = &s;
+    dev.rk = rk ? rk->d : nullptr;
+    for (std::size_t i = 0; i < nslot; ++i) dev.slot.push_back(s.take(Bc * S0));
+    dev.T3 = s.take(Bc * 3 * l0 * N);
+    dev.Y = s.take(2 * Bc * N);
+    dev.Z = s.take(2 * Bc * l0 * N);
+    const std::size_t So = 2 * res.level * N;
+    for (std::size_t b0 = 0; b0 < B; b0 += Bc) {
+        const std::size_t cnt = std::min(Bc, B - b0);
+        dev.B = (int)cnt;
+        for (std::size_t b = 0; b < cnt; ++b) d2d(c, dev.slot[0] + b * S0, x[b0 + b]->d, S0);
+        const MathVal r = dev.run(fn, a, iters, l0, x[0]->scale);
+        for (std::size_t b = 0; b < cnt; ++b) {
+            hec_ciphertext *o = out[b0 + b];
+            grow(o, So);
+            d2d(c, o->d, dev.slot[(std::size_t)r.slot] + b * So, So);
+            o->size = 2;
+            o->level = r.level;
+            o->scale = r.scale;
+        }
+    }
+}
+}  // namespace
+
+int hec_math_plan(const uint64_t *coeff_modulus, uint64_t K, int fn, double a, uint64_t iter_num, uint64_t level,
+                  double scale, uint64_t *out_level, double *out_scale)
+{
+    return guard([&] {
+        need(coeff_modulus && out_level && out_scale, "null argument");
+        need(K >= 2 && K - 1 <= HEC_MAXL, "coeff_modulus size is not valid");
+        need(fn >= HEC_MATH_SIGNED_INV && fn <= HEC_MATH_ABS, "unknown he::math function");
+        need(level >= 1 && level <= K - 1, BAD_CT);
+        need(iter_num >= 1, "iter_num must be positive");
+        MathRun plan;
+        plan.ch = Chain{coeff_modulus, (std::size_t)(K - 1)};
+        const MathVal r = plan.run(fn, a, iter_num, level, scale);
+        *out_level = r.level;
+        *out_scale = r.scale;
+    });
+}
+
+int hec_math_signed_inv(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                        const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { math_batch(ctx, HEC_MATH_SIGNED_INV, x, B, a, iter_num, rk, out); });
+}
+int hec_math_inv_sqrt_twice(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                            const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { math_batch(ctx, HEC_MATH_INV_SQRT_TWICE, x, B, a, iter_num, rk, out); });
+}
+int hec_math_sqrt(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                  const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { math_batch(ctx, HEC_MATH_SQRT, x, B, a, iter_num, rk, out); });
+}
+int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                 const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { math_batch(ctx, HEC_MATH_ABS, x, B, a, iter_num, rk, out); });
+}
+int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels)
+{
+    return guard([&] { math_batch(ctx, -1, cts, B, 0.0, levels, nullptr, cts); });
 }
 
 // ------------------------------------------------------------------ multi-GPU

@@ -140,6 +140,8 @@ struct Ctx {
     bool kernel_memops = true;
     int prng_group = 0;            // option "prng_group": PRNG buffers per wavefront of k_prng (hec_keygen.hip), 1 .. 16;
                                    // 0 picks the largest that still fills the device.  Every value draws the same words
+    int math_chunk = 0;            // option "math_chunk": ciphertexts per pass of the he::math calls, 0 automatic (the
+                                   // 65,535 y-blocks of an NTT launch bound it).  Every value computes the same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -315,5 +317,15 @@ void fft_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_
 void fft_round_limbs(Ctx &c, const u64 *Y, u64 *Z, int nsrc, int nk, int l);
 void fft_mrs(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, const u64 *P, u64 p_sp, PolyArr OUT, int nout,
              int nk, int l, int half, int nb, int nt);
+
+// he::math stage kernels (hec_kernels.hip, MathIOB / k_math_tensor).  Scalar stage OUT = rescale(A (*) c) + d over B
+// entries of nk polys at level l: math_lastprod forms the last-limb products Y (then the batched INTT and
+// fft_round_limbs give Z), math_cstage is the fused pass B; cw / dw hold one word per limb (dw null: nothing added, and
+// d meets poly 0 only).  math_tensor: OUT[b] = A[b] (x) (Bp[b] + d) in the [B][3][l][N] layout keyswitch() takes; Bp
+// equal to A squares
+void math_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, u64 *Y, int B, int nk, int l, u64 cw);
+void math_cstage(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, PolyArr OUT, int B, int nk, int l,
+                 const u64 *cw, const u64 *dw);
+void math_tensor(Ctx &c, PolyArr A, PolyArr Bp, const u64 *dw, u64 *OUT, int B, int l);
 
 }  // namespace hec

@@ -1306,6 +1306,188 @@ void fft_mrs(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, const u64 *
     ntt_dispatch<false>(c, nout * nk * nl, DivRoundIO_A{}, b, 2);
 }
 
+// =============================================================================== he::math ==
+// The scalar stage of he::math (math_cstage): OUT = rescale(A (*) c) + d, c and d scalar plaintexts.  A scalar
+// plaintext in NTT form is one word per limb (CKKSEncoder::encode of a double fills limb i with one residue), so c_i
+// and d_i travel in the kernel arguments and no plaintext buffer exists.  Pass B of the rounding limbs' NTT forms
+// a c_i at the store (kLatePre), subtracts NTT(z), multiplies by q_last^-1 and adds d_i on poly 0 alone (add_plain /
+// sub_plain touch c0 only; a subtraction arrives as q_i - d_i).  Every step is exact arithmetic mod q_i on canonical
+// inputs and the output is canonicalised once, so the bits equal multiply_plain, rescale_to_next, add_plain in turn.
+struct MathIOB {
+    const u64 *Z, *A;
+    u64 a_sb, a_sk;  // source entry / poly strides (limb stride N)
+    PolyArr OUT;
+    int nk, nl, logN;
+    const DevPrime *primes;
+    u64 c[HEC_MAXL], d[HEC_MAXL], inv[HEC_MAXL], inv_q[HEC_MAXL];
+    struct Bound {
+        static constexpr bool kFpStore = true;
+        static constexpr bool kLatePre = true;  // the operand is loaded at the store: one word per output in flight
+        const u64 *z, *a;
+        u64 *out;
+        DevPrime pr;
+        u64 c, d, w, wq;
+        int prime;
+        bool fpstore = true;
+        bool valid = true;
+        struct Pre {
+            u64 x;  // a c mod q, canonical
+        };
+        __device__ Pre pre(u64 g) const
+        {
+            if (pr.fp) return Pre{fp_canon(fp_mulmod(u2d(a[g]), u2d(c), pr.qd, pr.qinv), pr.qd, pr.qinv)};
+            return Pre{mulmod(a[g], c, pr)};
+        }
+        __device__ u64 load(u64 g) const { return z[g]; }
+        __device__ void store(u64 g, u64 v, Pre p) const
+        {
+            st1m<2>(out + g, addmod(shoup(p.x + pr.q - v, w, wq, pr.q), d, pr.q));
+        }
+        // |x - v| < 11 q as in DivRoundIOB; the product lies in [-0.53 q, 0.53 q], d in [0, q)
+        __device__ void store_fp(u64 g, double v, Pre p, const DevPrime &) const
+        {
+            const double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv) + u2d(d);
+            st1m<2>(out + g, fp_canon(r, pr.qd, pr.qinv));
+        }
+    };
+    __device__ Bound bind(int job) const
+    {
+        const int i = job % nl, t = job / nl, k = t % nk, b = t / nk;
+        const u64 li = (u64)i << logN;
+        Bound bo;
+        bo.z = Z + ((u64)job << logN);
+        bo.a = A + (u64)b * a_sb + (u64)k * a_sk + li;
+        bo.out = OUT.p + b * OUT.sb + k * OUT.sk + li;
+        bo.pr = primes[i];
+        bo.c = c[i];
+        bo.d = k == 0 ? d[i] : 0;
+        bo.w = inv[i];
+        bo.wq = inv_q[i];
+        bo.prime = i;
+        return bo;
+    }
+};
+
+// Y[(b nk + k)][g] = A[b][k][last][g] c_last mod q_last: the last-limb products of the scalar stage, two words (16
+// bytes) per lane
+__global__ void __launch_bounds__(256)
+    k_math_lastprod(const u64 *__restrict__ A, u64 a_sb, u64 a_sk, u64 *__restrict__ Y, int nk, int logN, int last,
+                    u64 cw, u64 pairs, const DevPrime *__restrict__ primes)
+{
+    const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pairs) return;
+    const u64 idx = 2 * p, g = idx & ((1ull << logN) - 1), t = idx >> logN;
+    const int k = (int)(t % nk);
+    const u64 b = t / nk;
+    const DevPrime pr = primes[last];
+    const ulonglong2 a = ld2(A + b * a_sb + (u64)k * a_sk + ((u64)last << logN), g);
+    u64 x, y;
+    if (pr.fp) {
+        const double cd = u2d(cw);
+        x = fp_canon(fp_mulmod(u2d(a.x), cd, pr.qd, pr.qinv), pr.qd, pr.qinv);
+        y = fp_canon(fp_mulmod(u2d(a.y), cd, pr.qd, pr.qinv), pr.qd, pr.qinv);
+    } else {
+        x = mulmod(a.x, cw, pr);
+        y = mulmod(a.y, cw, pr);
+    }
+    st2(Y, idx, x, y);
+}
+
+void math_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, u64 *Y, int B, int nk, int l, u64 cw)
+{
+    const u64 pairs = (u64)B * nk * c.N / 2;
+    k_math_lastprod<<<(unsigned)((pairs + 255) / 256), 256, 0, c.stream>>>(A, a_sb, a_sk, Y, nk, c.logN, l - 1, cw, pairs,
+                                                                          c.primes);
+    HEC_HIP(hipGetLastError());
+}
+
+// the scalar stage's pass B (MathIOB) over B entries of nk polys at level l -> OUT at level l - 1; Z from
+// fft_round_limbs; dw == nullptr: no constant is added
+void math_cstage(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, PolyArr OUT, int B, int nk, int l,
+                 const u64 *cw, const u64 *dw)
+{
+    const int nl = l - 1;
+    if (nl < 1 || nl > HEC_MAXL) throw std::invalid_argument("math_cstage: 1 to HEC_MAXL output limbs");
+    MathIOB b{};
+    b.Z = Z; b.A = A; b.a_sb = a_sb; b.a_sk = a_sk; b.OUT = OUT; b.nk = nk; b.nl = nl; b.logN = c.logN;
+    b.primes = c.primes;
+    for (int i = 0; i < nl; ++i) {
+        b.c[i] = cw[i];
+        b.d[i] = dw ? dw[i] : 0;
+        b.inv[i] = c.ql_inv[l][i];
+        b.inv_q[i] = c.ql_inv_q[l][i];
+    }
+    ntt_dispatch<false>(c, B * nk * nl, DivRoundIO_A{}, b, 2);
+}
+
+// The product stage's tensor (k_math_tensor): OUT[b] = A[b] (x) (B'[b] + d), sizes 2 x 2 -> 3, B jobs along grid y,
+// in the [B][3][l][N] layout keyswitch() takes.  same: B' is A (the square), each word read once.  d (has_d): a
+// scalar plaintext's words added to B'.c0 on load, so the operand "e^2 + 1" of signed_inv is never stored.  Products as
+// SEAL reduces them, FP64 for the primes below 2^42 (exact fp_mulmod, |sum| <= 1.06 q) and 128-bit sums otherwise;
+// canonical outputs, so the bits are those of multiply / square after add_plain.  Two words (16 bytes) per lane.
+struct MathConst {
+    u64 d[HEC_MAXL];
+};
+__global__ void __launch_bounds__(256)
+    k_math_tensor(PolyArr A, PolyArr Bp, int same, int has_d, MathConst dc, u64 *__restrict__ OUT, int l, int logN,
+                  u64 pairs, const DevPrime *__restrict__ primes)
+{
+    const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pairs) return;
+    const u64 idx = 2 * p, b = blockIdx.y;
+    const int i = (int)(idx >> logN);
+    const DevPrime pr = primes[i];
+    const u64 *a = A.p + b * A.sb;
+    const ulonglong2 a0 = ld2(a, idx), a1 = ld2(a + A.sk, idx);
+    ulonglong2 b0 = a0, b1 = a1;
+    if (!same) {
+        const u64 *bp = Bp.p + b * Bp.sb;
+        b0 = ld2(bp, idx);
+        b1 = ld2(bp + Bp.sk, idx);
+    }
+    if (has_d) {
+        const u64 d = dc.d[i];
+        b0.x = addmod(b0.x, d, pr.q);
+        b0.y = addmod(b0.y, d, pr.q);
+    }
+    u64 r0[2], r1[2], r2[2];
+    const u64 av0[2] = {a0.x, a0.y}, av1[2] = {a1.x, a1.y}, bv0[2] = {b0.x, b0.y}, bv1[2] = {b1.x, b1.y};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        if (pr.fp) {
+            const double x0 = u2d(av0[e]), x1 = u2d(av1[e]), y0 = u2d(bv0[e]), y1 = u2d(bv1[e]);
+            r0[e] = fp_canon(fp_mulmod(x0, y0, pr.qd, pr.qinv), pr.qd, pr.qinv);
+            r1[e] = fp_canon(fp_mulmod(x0, y1, pr.qd, pr.qinv) + fp_mulmod(x1, y0, pr.qd, pr.qinv), pr.qd, pr.qinv);
+            r2[e] = fp_canon(fp_mulmod(x1, y1, pr.qd, pr.qinv), pr.qd, pr.qinv);
+        } else {
+            U128 m{av0[e] * bv1[e], mulhi64(av0[e], bv1[e])};
+            mac128(m, av1[e], bv0[e]);
+            r0[e] = mulmod(av0[e], bv0[e], pr);
+            r1[e] = barrett128(m.lo, m.hi, pr.q, pr.r0, pr.r1);
+            r2[e] = mulmod(av1[e], bv1[e], pr);
+        }
+    }
+    const u64 ps = (u64)l << logN;
+    u64 *o = OUT + b * 3 * ps;
+    st2(o, idx, r0[0], r0[1]);
+    st2(o + ps, idx, r1[0], r1[1]);
+    st2(o + 2 * ps, idx, r2[0], r2[1]);
+}
+
+void math_tensor(Ctx &c, PolyArr A, PolyArr Bp, const u64 *dw, u64 *OUT, int B, int l)
+{
+    if (l < 1 || l > HEC_MAXL) throw std::invalid_argument("math_tensor: 1 to HEC_MAXL limbs");
+    if (B < 1 || B > 65535) throw std::invalid_argument("math_tensor: 1 to 65535 jobs");
+    MathConst dc{};
+    if (dw)
+        for (int i = 0; i < l; ++i) dc.d[i] = dw[i];
+    const u64 pairs = (u64)l * c.N / 2;
+    const bool same = Bp.p == A.p && Bp.sb == A.sb && Bp.sk == A.sk;
+    k_math_tensor<<<dim3((unsigned)((pairs + 255) / 256), (unsigned)B), 256, 0, c.stream>>>(
+        A, Bp, same ? 1 : 0, dw ? 1 : 0, dc, OUT, l, c.logN, pairs, c.primes);
+    HEC_HIP(hipGetLastError());
+}
+
 // =============================================================== fan-out: INTT pass A -> fwd passes A ==
 // A block owns NSEG columns (R rows) of one source limb whose inverse pass B already ran.  It finishes
 // the INTT (inverse pass A, N^-1 scaling, canonical residues), keeps the coefficient-form column values

@@ -86,7 +86,8 @@ int hec_context_synchronize(hec_context *ctx);
  * bit-identical.  Applies to the context and its batch lanes; HEC_EINVAL for an unknown name, and for a value
  * outside an enumerated knob's range ("split_bfly" 0..4, "hmac" 0..2, "hmac_odd3" 0..1, "hoist_scan" 0..1,
  * "nttb_shfl" 0..2, "nttb_shfl_dr" 0..1, "moddown1" 0..1, "hmac_int" 0..1, "nt_e" 0..1,
- * "mac_divround" 0..1, "prng_group" 0..16). */
+ * "mac_divround" 0..1, "prng_group" 0..16).  "math_chunk" (0..65535) caps the ciphertexts per pass of the he::math
+ * calls below; 0 is automatic, a negative value HEC_EINVAL. */
 int hec_context_set_option(hec_context *ctx, const char *name, int64_t value);
 uint64_t hec_context_poly_degree(const hec_context *ctx);
 uint64_t hec_context_key_moduli(const hec_context *ctx); /* K */
@@ -322,6 +323,42 @@ int hec_fft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t n, int i
  * NAF terms; "Galois key not present").  Errors as hec_fft, and n <= slot_count ("n must be at most slot_count"). */
 int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint64_t n, int inverse,
              const hec_galois_keys *gk, hec_ciphertext *const *out);
+
+/* ---------------------------------------------------------------- he::math ----------------- */
+/* The reference's he::math (src/core/he_math.cpp:22-269) on B ciphertexts at once.  out[i] is, bit for bit with its
+ * level and scale, what the per-operation schedule (scalar encodes at the ciphertext's parms_id and scale,
+ * multiply_plain, multiply / square, relinearize, rescale_to_next, add_plain / sub_plain, sub) gives for x[i] alone;
+ * every stage of that schedule runs once over the whole batch.  B >= 1; every x[i] of size 2 ("encrypted size must be
+ * 2"), at one level ("encrypted1 and encrypted2 parameter mismatch"), with bitwise-equal scales ("scale mismatch");
+ * iter_num >= 1 ("iter_num must be positive"; the reference asserts); rk of this context ("relin_keys is not valid
+ * for encryption parameters").  The host checks of the whole schedule run first, in the schedule's order, and the
+ * first that fails is the call's status and message ("scale out of bounds", "end of modulus switching chain
+ * reached", "encoded value is too large", "scale mismatch"); nothing is written on an error.  out[i] may be a fresh
+ * handle or x[i].  Ordered on the context's stream; a batch larger than one pass allows (65,535 blocks per NTT
+ * launch, or the option "math_chunk") runs in several passes. */
+#define HEC_MATH_SIGNED_INV 0
+#define HEC_MATH_INV_SQRT_TWICE 1
+#define HEC_MATH_SQRT 2
+#define HEC_MATH_ABS 3
+/* host only, no device: the level and scale the call below would return for inputs at (level, scale), or the status
+ * and message of the first check that the per-operation sequence would fail.  coeff_modulus: the K key moduli */
+int hec_math_plan(const uint64_t *coeff_modulus, uint64_t K, int fn, double a, uint64_t iter_num, uint64_t level,
+                  double scale, uint64_t *out_level, double *out_scale);
+/* signed_inv (he_math.cpp:22-90): 1/x = a prod_k (1 + (1 - a x)^(2^k)) from 2a - a^2 x; |a x - 1| < 1 */
+int hec_math_signed_inv(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                        const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* inv_sqrt_twice (he_math.cpp:95-164, the `#if 1` form): Newton for 1/sqrt(2x), y' = 3/2 y - x y^3 from y0 = a */
+int hec_math_inv_sqrt_twice(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                            const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* sqrt (he_math.cpp:211-232): inv_sqrt_twice(x, 1 / a / sqrt 2) times sqrt(2) x dropped to its level */
+int hec_math_sqrt(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                  const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* abs (he_math.cpp:237-269): inv_sqrt_twice(x^2, 1 / a / sqrt 2) times sqrt(2) x^2 dropped to its level */
+int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
+                 const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* he::util::drop_chain_levels (he_util.h:27-48) on B ciphertexts in place: per level, every ciphertext times the
+ * scalar encode of 1 at the first one's level and scale, rescaled.  Inputs and errors as above; levels = 0 is a no-op */
+int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels);
 
 /* ---------------------------------------------------------------- multi-GPU (SURVEY 8(b),(e)) */
 /* One process per GPU.  The reference is single-threaded (no collective anywhere); the sharded matvec splits
