@@ -176,6 +176,9 @@ def lib():
             "hec_math_sqrt": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
             "hec_math_abs": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
             "hec_drop_chain_levels": [vp, vp, C.c_uint64, C.c_uint64],
+            "hec_multiply_relin_rescale_many": [vp, vp, vp, C.c_uint64, vp, vp],
+            "hec_sum_elems_many": [vp, vp, C.c_uint64, C.c_uint64, vp, vp],
+            "hec_sum_elems_plan": [C.c_uint64, C.POINTER(C.c_int), C.c_uint64, u64p],
             "hec_keygen_secret": [vp, u64p, C.POINTER(vp)],
             "hec_keygen_public": [vp, vp, u64p, C.POINTER(vp)],
             "hec_public_key_upload": [vp, u64p, C.POINTER(vp)],
@@ -481,6 +484,24 @@ def math_plan(moduli, fn, a, iters, level, scale):
     _check(lib().hec_math_plan(_p(m), len(m), int(fn), float(a), int(iters), int(level), float(scale), C.byref(lv),
                                C.byref(sc)))
     return lv.value, sc.value
+
+
+def sum_elems_plan(dim, cap=None):
+    """hec_sum_elems_plan (host only): the rotation steps Context.sum_elems issues for dim, in order, the ones whose
+    result the schedule discards included (dim = 1 rotates once and keeps the input).  cap: the size of the buffer
+    handed to the engine (default: as many as the plan holds); with a smaller one, (steps written, count) is
+    returned."""
+    n = C.c_uint64()
+    _check(lib().hec_sum_elems_plan(int(dim), None, 0, C.byref(n)))
+    if cap is None:
+        buf = (C.c_int * max(1, n.value))()
+        _check(lib().hec_sum_elems_plan(int(dim), buf, n.value, C.byref(n)))
+        return list(buf[:n.value])
+    buf = (C.c_int * (int(cap) + 1))(*([-1] * (int(cap) + 1)))  # one guard word behind the cap
+    _check(lib().hec_sum_elems_plan(int(dim), buf, int(cap), C.byref(n)))
+    if buf[int(cap)] != -1:
+        raise RuntimeError("hec_sum_elems_plan wrote past its cap")
+    return list(buf[:min(int(cap), n.value)]), n.value
 
 
 def create_coeff_modulus(N, bits):
@@ -838,6 +859,35 @@ class Context:
         lst = [cts] if single else list(cts)
         _check(lib().hec_drop_chain_levels(self.h, self._arr(lst), len(lst), int(levels)))
         return cts
+
+    # -------------------------------------------------------------- he::linalg element-wise products and sums
+    def _batch(self, cts, out):
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        if out is None:
+            out = [Ciphertext(self) for _ in cts]
+        elif isinstance(out, Ciphertext):
+            out = [out]
+        return single, cts, out
+
+    def multiply_relin_rescale(self, a, b, rk, out=None):
+        """hec_multiply_relin_rescale_many: rescale_to_next(relinearize(a[i] * b[i], rk)) for every pair of the lists
+        (or for one pair, then one ciphertext is returned); b is a, or equal handles, squares.  The entries may sit
+        at different levels and scales."""
+        single, la, out = self._batch(a, out)
+        lb = la if b is a else ([b] if isinstance(b, Ciphertext) else list(b))
+        if len(lb) != len(la):
+            raise ValueError("a and b must have the same length")
+        _check(lib().hec_multiply_relin_rescale_many(self.h, self._arr(la), self._arr(lb), len(la), rk.h,
+                                                     self._arr(out)))
+        return out[0] if single else out
+
+    def sum_elems(self, cts, dim, gk, out=None):
+        """hec_sum_elems_many: BatchedVector::sum_elems_inplace with this dim on every ciphertext of the list (or on
+        one, then one is returned); gk must hold the key of every step of sum_elems_plan(dim)."""
+        single, cts, out = self._batch(cts, out)
+        _check(lib().hec_sum_elems_many(self.h, self._arr(cts), len(cts), int(dim), gk.h, self._arr(out)))
+        return out[0] if single else out
 
     def reduce(self, ct):
         """Reduce every word of ct mod its prime (after a partial-sum exchange)."""

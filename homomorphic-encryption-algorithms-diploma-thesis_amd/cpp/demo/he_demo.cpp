@@ -21,6 +21,9 @@
 //          mathb:<iter>   (the same four functions through he_math.h's vector overloads, each on all n input
 //                          ciphertexts as one batch: signed_inv(., 1.0), inv_sqrt_twice(., 0.7), sqrt(., 1.0),
 //                          abs(., 1.0); 4 n outputs in that order)
+//          linalgb:<dim>  (the he_linalg.h members that are one batched engine call: with M the BatchedMatrix of the n input
+//                          ciphertexts as vectors of dimension <dim>, eval % rk % M * M, M.square, M.sum_bvec_elems, then
+//                          eval % rk % A * A for the inputs as a 1 x n Matrix; 4 n outputs in that order)
 //          util           (he::util: drop_chain_levels(c0, 2), then reach_chain_level of {c1, c2} to c0's level,
 //                          include/he_util.h:27-77; the chain indices of every output are printed)
 //          least_squares  (src/demos/matrix_operations.cpp:915-1003 on x = c0, y = c1 of 5 data slots: the sums,
@@ -231,7 +234,7 @@ int selfcontained(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
     if (argc != 4) {
-        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|math:<iter>|mathb:<iter>|"
+        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|linalgb:<dim>|math:<iter>|mathb:<iter>|"
                      "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|selfcontained|server> <in.bin> <out.bin>\n";
         return 1;
     }
@@ -335,6 +338,20 @@ int main(int argc, char **argv)
         BatchedMatrix m(BatchedMatrix::BatchingType::col, std::move(bvecs));
         BatchedMatrix s = m.sum_bvec_elems(eval, gk);
         for (const auto &b : s.get_bvecs()) keep.push_back(b.get_bvec());
+    } else if (mode.rfind("linalgb:", 0) == 0) {
+        // the members of he_linalg.h that run one batched engine call over all their ciphertexts: every input as a
+        // batched vector of dimension <dim> of one BatchedMatrix M: eval % rk % M * M, M.square, M.sum_bvec_elems,
+        // then the element-wise eval % rk % A * A of the inputs as a 1 x n Matrix
+        const std::size_t dim = std::stoul(mode.substr(8));
+        std::vector<BatchedVector> bvecs;
+        for (auto &c : cts) bvecs.emplace_back(dim, c);
+        BatchedMatrix M(BatchedMatrix::BatchingType::col, std::move(bvecs));
+        const BatchedMatrix MM = eval % rk % M * M, M2 = M.square(eval, rk), S = M.sum_bvec_elems(eval, gk);
+        for (const BatchedMatrix *r : {&MM, &M2, &S})
+            for (const auto &b : r->get_bvecs()) keep.push_back(b.get_bvec());
+        const Matrix A(1, cts.size(), cts);
+        const Matrix AA = eval % rk % A * A;
+        for (const auto &c : AA.get_elems()) keep.push_back(c);
     } else if (mode == "matrix_family") {
         // Matrix::left_matmul_with_transp, matmul_square, matmul_pow (he_linalg.cpp:241-349) on the first four
         // ciphertexts as a 2x2 column-major matrix, then matmul_pow(3), which needs operands of two levels

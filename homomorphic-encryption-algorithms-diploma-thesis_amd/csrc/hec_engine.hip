@@ -378,14 +378,23 @@ std::size_t ks_words(const Ctx &c, std::size_t B, std::size_t l)
     return c.N * B * (l + (l + 1) * l + 2 * (l + 1) + 2 * l) + 4 * 64;
 }
 
+// the separate add of a key switch's optional addend: OUT += ADD (both polys), where the last stage did not add it
+static void add_after(Ctx &c, PolyArr OUT, PolyArr ADD, int B, int l)
+{
+    ProfScope k(c, "k:k_ew_add/rot_add", 6.0 * B * l);  // two ciphertexts read, one written
+    ew_add(c, OUT, ADD, OUT, B, 2, l, 0);
+}
+
 // key-switch mod-down (SEAL switch_key_inplace step 4): the P-limb INTT's first pass, the fan-out that
 // finishes it and forms the rounding limbs, and divide_round's pass B (OUT = IN + (ACC_i - r) P^-1)
 // single-pass form (c.moddown1, N = 2^15): the P limbs' whole INTT in place, then k_moddown1 forms each data limb's
 // rounding limb, transforms it and divides-and-rounds in one kernel (no Z round trip, no fan-out, no pass B)
+// ADD (optional, ng == 1): a second addend of both polys, unpermuted, added in the kernel's store (may be OUT[0])
 static bool moddown_single(Ctx &c, u64 *ACC, PolyArr IN, int in_nk, const PolyArr *OUT, const u32 *elts, int ng, int B,
-                           int l)
+                           int l, PolyArr ADD = PolyArr{})
 {
     if (!c.moddown1 || c.logN != 15) return false;
+    if (ADD.p && ng != 1) throw std::logic_error("moddown_single: an addend with sibling rotations");
     const u64 N = c.N, sacc = (u64)B * 2 * (l + 1) * N;
     ProfScope ps(c, "ks_moddown");
     const int pP[1] = {(int)c.K - 1};
@@ -393,17 +402,21 @@ static bool moddown_single(Ctx &c, u64 *ACC, PolyArr IN, int in_nk, const PolyAr
         ProfScope k(c, "k:k_ntt/moddown_intt", 8.0 * B * ng, 2);
         ntt_strided(c, true, ACC + l * N, (l + 1) * N, ACC + l * N, (l + 1) * N, 1, pP, 2 * B * ng, 1, 3);
     }
-    for (int q = 0; q < ng; ++q) {  // P limb (2B, once per (b, k)), ACC (2Bl), IN (in_nk B l), OUT (2Bl)
-        ProfScope k(c, "k:k_moddown1/moddown", (2.0 + (4.0 + in_nk) * l) * B, 2);  // one launch per class
+    for (int q = 0; q < ng; ++q) {  // P limb (2B, once per (b, k)), ACC (2Bl), IN (in_nk B l), OUT (2Bl), ADD (2Bl)
+        ProfScope k(c, ADD.p ? "k:k_moddown1/moddown_add" : "k:k_moddown1/moddown",
+                    (2.0 + (4.0 + in_nk + (ADD.p ? 2.0 : 0.0)) * l) * B, 2);  // one launch per class
         moddown1(c, ACC + q * sacc + l * N, 2 * (l + 1) * N, (l + 1) * N, PolyArr{ACC + q * sacc, 2 * (l + 1) * N, (l + 1) * N},
-                 IN, in_nk, OUT[q], B, 2, l, (int)c.K - 1, elts[q]);
+                 IN, in_nk, OUT[q], B, 2, l, (int)c.K - 1, elts[q], ADD);
     }
     return true;
 }
 
-void moddown(Ctx &c, u64 *ACC, u64 *Z, PolyArr IN, int in_nk, PolyArr OUT, int B, int l, u32 elt)
+// ADD (optional): OUT = ... + ADD as well, both polys, unpermuted (may be OUT).  k_moddown1 adds it in its store; the
+// two-pass forms run k_ew_add after themselves
+void moddown(Ctx &c, u64 *ACC, u64 *Z, PolyArr IN, int in_nk, PolyArr OUT, int B, int l, u32 elt,
+             PolyArr ADD = PolyArr{})
 {
-    if (moddown_single(c, ACC, IN, in_nk, &OUT, &elt, 1, B, l)) return;
+    if (moddown_single(c, ACC, IN, in_nk, &OUT, &elt, 1, B, l, ADD)) return;
     const u64 N = c.N;
     const bool fan = c.fan_out;
     ProfScope ps(c, "ks_moddown");
@@ -421,6 +434,7 @@ void moddown(Ctx &c, u64 *ACC, u64 *Z, PolyArr IN, int in_nk, PolyArr OUT, int B
         divide_round(c, ACC + l * N, 2 * (l + 1) * N, (l + 1) * N, PolyArr{ACC, 2 * (l + 1) * N, (l + 1) * N}, IN,
                      in_nk, OUT, B, 2, l, (int)c.K - 1, c.p_inv.data(), c.p_inv_q.data(), Z, elt, fan ? 2 : 3);
     }
+    if (ADD.p) add_after(c, OUT, ADD, B, l);
 }
 
 // The mod-downs of ng sibling rotations of one node at once: ACC[q] = ACC + q B 2 (l+1) N (contiguous), IN the
@@ -455,9 +469,18 @@ void moddown_group(Ctx &c, u64 *ACC, u64 *Z, PolyArr IN, int in_nk, const PolyAr
 
 // T (the target polys) and IN (added to the output) are read through the Galois permutation of elt
 // (elt = 1: as they are).  OUT must not overlap T or IN when elt != 1 (the reads gather).
+// ADD (optional): a second addend of both output polys, OUT = (acc - NTT(z)) P^-1 + perm(IN) + ADD, read unpermuted at
+// the words a thread writes, so ADD may be OUT: the accumulate step acc' = acc + rotate(src, step) of a sum over
+// slots as one key switch.  Added in the last stage's store by k_bmac's divide-and-round epilogue and by k_moddown1
+// (option "rot_add" = 1, the default); by a k_ew_add launch after every other path, and after all with "rot_add" = 0
 void keyswitch(Ctx &c, Scratch &s, PolyArr T, const u64 *key, PolyArr IN, int in_nk, PolyArr OUT, int B, int l,
-               u32 elt = 1)
+               u32 elt = 1, PolyArr ADD = PolyArr{})
 {
+    if (ADD.p && !c.rot_add) {
+        keyswitch(c, s, T, key, IN, in_nk, OUT, B, l, elt);
+        add_after(c, OUT, ADD, B, l);
+        return;
+    }
     const u64 N = c.N;
     const std::size_t top = s.top;
     u64 *D = s.take(B * l * N), *E = s.take((u64)B * (l + 1) * l * N), *ACC = s.take((u64)B * 2 * (l + 1) * N),
@@ -496,13 +519,15 @@ void keyswitch(Ctx &c, Scratch &s, PolyArr T, const u64 *key, PolyArr IN, int in
                 ProfScope k(c, "k:k_fan2/moddown", 2.0 * B * (l + 1));
                 fan_divide_round(c, ACC + l * N, 2 * (l + 1) * N, (l + 1) * N, Z, B, 2, l, (int)c.K - 1);
             }
-            {  // digits E (B l (l - 1)) + targets (B l) + key (2 l l) + Z (2 B l) + IN (in_nk B l) -> OUT (2 B l)
+            {  // digits E (B l (l - 1)) + targets (B l) + key (2 l l) + Z (2 B l) + IN (in_nk B l) -> OUT (2 B l);
+               // with ADD its 2 B l as well
                 ProfScope ps(c, "ks_bmac");
-                ProfScope k(c, "k:k_bmac/divround", (double)B * l * l + 2.0 * l * l + (4.0 + in_nk) * B * l, 1);
+                ProfScope k(c, ADD.p ? "k:k_bmac/divround_add" : "k:k_bmac/divround",
+                            (double)B * l * l + 2.0 * l * l + (4.0 + in_nk + (ADD.p ? 2.0 : 0.0)) * B * l, 1);
                 BmacDR dr{};
                 dr.Z = Z; dr.IN = IN; dr.OUT = OUT; dr.in_nk = in_nk;
                 for (int i = 0; i < l; ++i) { dr.inv[i] = c.p_inv[i]; dr.inv_q[i] = c.p_inv_q[i]; }
-                ks_modup_mac(c, D, E, T, key, ACC, B, l, 2, elt, &dr, 2);
+                ks_modup_mac(c, D, E, T, key, ACC, B, l, 2, elt, &dr, 2, ADD.p ? &ADD : nullptr);
             }
             s.top = top;
             return;
@@ -523,7 +548,7 @@ void keyswitch(Ctx &c, Scratch &s, PolyArr T, const u64 *key, PolyArr IN, int in
             ks_mac(c, T, E, key, ACC, B, l, elt);
         }
     }
-    moddown(c, ACC, Z, IN, in_nk, OUT, B, l, elt);
+    moddown(c, ACC, Z, IN, in_nk, OUT, B, l, elt, ADD);
     s.top = top;
 }
 
@@ -664,12 +689,14 @@ const u64 *galois_mkey(hec_context *ctx, hec_galois_keys &gk, u32 elt)
 // When OUT does not alias X the permutation is applied inside the key switch's loads (the INTT of c1,
 // the target reuse in the MAC, the c0 add in the mod-down) and never materialised; otherwise X is
 // first permuted into scratch.
-void galois_ks(Ctx &c, Scratch &s, PolyArr X, PolyArr OUT, int B, int l, u32 elt, const u64 *key)
+// ADD (optional): OUT = that + ADD (keyswitch's second addend; ADD may be OUT, and may be X when OUT is not)
+void galois_ks(Ctx &c, Scratch &s, PolyArr X, PolyArr OUT, int B, int l, u32 elt, const u64 *key,
+               PolyArr ADD = PolyArr{})
 {
     const u64 N = c.N;
     const bool alias = OUT.p == X.p || !c.fuse_galois;
     if (!alias) {
-        keyswitch(c, s, PolyArr{X.p + X.sk, X.sb, 0}, key, PolyArr{X.p, X.sb, X.sk}, 1, OUT, B, l, elt);
+        keyswitch(c, s, PolyArr{X.p + X.sk, X.sb, 0}, key, PolyArr{X.p, X.sb, X.sk}, 1, OUT, B, l, elt, ADD);
         return;
     }
     const std::size_t top = s.top;
@@ -678,7 +705,7 @@ void galois_ks(Ctx &c, Scratch &s, PolyArr X, PolyArr OUT, int B, int l, u32 elt
         ProfScope ps(c, "galois");
         galois_permute(c, X, PolyArr{S, l * N, (u64)B * l * N}, B, 2, l, elt);
     }
-    keyswitch(c, s, PolyArr{S + (u64)B * l * N, l * N, 0}, key, PolyArr{S, l * N, 0}, 1, OUT, B, l);
+    keyswitch(c, s, PolyArr{S + (u64)B * l * N, l * N, 0}, key, PolyArr{S, l * N, 0}, 1, OUT, B, l, 1, ADD);
     s.top = top;
 }
 
@@ -1886,6 +1913,7 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "tensor_xcd") c.tensor_xcd = (int)std::max<int64_t>(0, value);
             else if (n == "prng_group") c.prng_group = in(0, 16);
             else if (n == "math_chunk") c.math_chunk = in(0, 65535);
+            else if (n == "rot_add") c.rot_add = in(0, 1);
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -3807,6 +3835,23 @@ namespace {
 constexpr int MATH_MAX_JOBS = 65535;  // blocks along y of one NTT pass
 constexpr std::size_t MATH_AUTO_CHUNK = 256;  // automatic ciphertexts per pass at most (workspace size)
 
+// The product stage over B ciphertexts at level l: OUT = rescale(relin(A (*) (Bp [+ dw]))) at level l - 1.  A and Bp
+// may be one array (the squares); T3: 3 B l N words for the size-3 products.  he::math's products and
+// hec_multiply_relin_rescale_many (dw == nullptr) run it
+void product_stage(Ctx &c, Scratch &s, PolyArr A, PolyArr Bp, const u64 *dw, u64 *T3, const u64 *rk, int B, int l,
+                   PolyArr OUT)
+{
+    const u64 N = c.N, S3 = 3 * (u64)l * N;
+    const bool same = A.p == Bp.p;
+    {
+        ProfScope k(c, "k:k_math_tensor/math", ((same ? 2.0 : 4.0) + 3.0) * B * l);
+        math_tensor(c, A, Bp, dw, T3, B, l);
+    }
+    const PolyArr Aa{T3, S3, (u64)l * N};
+    keyswitch(c, s, PolyArr{T3 + 2 * (u64)l * N, S3, 0}, rk, Aa, 2, Aa, B, l);
+    rescale_batch(c, s, Aa, B, 2, l, OUT);
+}
+
 struct MathVal {
     int slot = -1;
     std::size_t level = 0;
@@ -3908,17 +3953,7 @@ struct MathRun {
         o.level = l - 1;
         o.scale = ns / (double)ch.q[l - 1];
         o.slot = take();
-        if (c) {
-            const u64 N = c->N, S3 = 3 * l * N;
-            const bool same = a.slot == b.slot;
-            {
-                ProfScope k(*c, "k:k_math_tensor/math", ((same ? 2.0 : 4.0) + 3.0) * B * l);
-                math_tensor(*c, arr(a), arr(b), has_d ? dw : nullptr, T3, B, (int)l);
-            }
-            const PolyArr Aa{T3, S3, l * N};
-            keyswitch(*c, *s, PolyArr{T3 + 2 * l * N, S3, 0}, rk, Aa, 2, Aa, B, (int)l);
-            rescale_batch(*c, *s, Aa, B, 2, (int)l, arr(o));
-        }
+        if (c) product_stage(*c, *s, arr(a), arr(b), has_d ? dw : nullptr, T3, rk, B, (int)l, arr(o));
         return o;
     }
 
@@ -4147,6 +4182,239 @@ int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, d
 int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels)
 {
     return guard([&] { math_batch(ctx, -1, cts, B, 0.0, levels, nullptr, cts); });
+}
+
+// ------------------------------------------------------------------ he::linalg over many ciphertexts ------
+// Matrix::operator*=, BatchedMatrix::operator*= / square_inplace / sum_bvec_elems_inplace (reference
+// src/core/he_linalg.cpp) as stages over a batch.  The entries are grouped by level on the host (as dec_run groups
+// its inputs); a group's inputs are gathered into Scratch slots once, its stages run over the whole group (in passes
+// of at most 65,535 / ((l + 1) l) entries, as math_batch), and the outputs are scattered after the last stage.  Scales
+// are per entry and host bookkeeping only.
+namespace {
+struct LinalgPlan {  // class members: no C language linkage inside the C-ABI block
+// the rotation steps of BatchedVector::sum_elems_inplace (he_linalg.cpp:667-713) in order: to_sum's in-place
+// rotations by `window` and the accumulate rotations; dim = 1 rotates once and discards the result
+static std::vector<int> sum_elems_steps(uint64_t dim)
+{
+    need(dim >= 1, "dim must be positive");
+    need(dim < (1ull << 31), "step count too large");  // `window` is an int
+    std::vector<int> st;
+    int window = 1;
+    if (dim & 1) st.push_back(window);
+    for (uint64_t bits = dim >> 1; bits != 0; bits >>= 1) {
+        window <<= 1;
+        if (bits & 1) {
+            for (int steps = window >> 1; steps != 0; steps >>= 1) st.push_back(steps);
+            if (bits != 1) st.push_back(window);
+        }
+    }
+    return st;
+}
+
+// the caller's entries by level (ascending), the caller's order kept inside a level
+static std::map<std::size_t, std::vector<std::size_t>> by_level(const hec_ciphertext *const *x, uint64_t B)
+{
+    std::map<std::size_t, std::vector<std::size_t>> g;
+    for (uint64_t i = 0; i < B; ++i) g[x[i]->level].push_back(i);
+    return g;
+}
+};
+std::size_t linalg_chunk(const Ctx &c, std::size_t l, std::size_t n)
+{
+    std::size_t Bc = std::min<std::size_t>(MATH_AUTO_CHUNK, std::max<std::size_t>(1, MATH_MAX_JOBS / ((l + 1) * l)));
+    if (c.math_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.math_chunk);
+    return std::min(Bc, n);
+}
+// an output written by one pass must not be an input that a later pass gathers
+void check_out_alias(const std::vector<const hec_ciphertext *const *> &ins, hec_ciphertext *const *out, uint64_t B)
+{
+    std::map<const hec_ciphertext *, uint64_t> o;
+    for (uint64_t i = 0; i < B; ++i)
+        need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
+    for (const hec_ciphertext *const *in : ins)
+        for (uint64_t i = 0; i < B; ++i) {
+            const auto it = o.find(in[i]);
+            need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
+        }
+}
+void scatter(Ctx &c, hec_ciphertext *o, const u64 *src, std::size_t words, std::size_t level, double scale)
+{
+    grow(o, words);
+    d2d(c, o->d, src, words);
+    o->size = 2;
+    o->level = level;
+    o->scale = scale;
+}
+
+void product_many(hec_context *ctx, const hec_ciphertext *const *a, const hec_ciphertext *const *b, uint64_t B,
+                  const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    need(ctx != nullptr, "context is null");
+    if (B == 0) return;
+    need(a && b && out, "null argument");
+    set_device(ctx);
+    Ctx &c = ctx->c;
+    for (uint64_t i = 0; i < B; ++i) {  // multiply / square, relinearize, rescale_to_next on entry i
+        check_ct(ctx, a[i]);
+        check_ct(ctx, b[i]);
+        check_obj(ctx, out[i], BAD_CT);
+        need(a[i]->size == 2 && b[i]->size == 2, "encrypted size must be 2");
+        need(a[i]->level == b[i]->level, "encrypted1 and encrypted2 parameter mismatch");
+        need(scale_ok(c, a[i]->scale * b[i]->scale, a[i]->level), "scale out of bounds");
+        check_obj(ctx, rk, BAD_RK);
+        if (a[i]->level == 1) throw std::invalid_argument("end of modulus switching chain reached");
+    }
+    check_out_alias({a, b}, out, B);
+    const std::size_t N = c.N;
+    const auto groups = LinalgPlan::by_level(a, B);
+    std::size_t words = 0;
+    for (const auto &g : groups) {
+        const std::size_t l = g.first, Bc = linalg_chunk(c, l, g.second.size());
+        words = std::max(words, Bc * (2 * 2 * l * N + 2 * (l - 1) * N + 3 * l * N) + ks_words(c, Bc, l) +
+                                    rescale_words(c, Bc, 2, l) + 8 * 64);
+    }
+    Scratch s(c, words);
+    for (const auto &g : groups) {
+        const std::size_t l = g.first, S0 = 2 * l * N, So = 2 * (l - 1) * N, Bc = linalg_chunk(c, l, g.second.size());
+        s.top = 0;
+        u64 *A = s.take(Bc * S0), *Bp = s.take(Bc * S0), *O = s.take(Bc * So), *T3 = s.take(Bc * 3 * l * N);
+        for (std::size_t b0 = 0; b0 < g.second.size(); b0 += Bc) {
+            const std::size_t cnt = std::min(Bc, g.second.size() - b0);
+            bool same = true;
+            for (std::size_t k = 0; k < cnt; ++k) {
+                const std::size_t i = g.second[b0 + k];
+                d2d(c, A + k * S0, a[i]->d, S0);
+                same = same && a[i] == b[i];
+            }
+            if (!same)
+                for (std::size_t k = 0; k < cnt; ++k) d2d(c, Bp + k * S0, b[g.second[b0 + k]]->d, S0);
+            const PolyArr Aa{A, S0, l * N};
+            product_stage(c, s, Aa, same ? Aa : PolyArr{Bp, S0, l * N}, nullptr, T3, rk->d, (int)cnt, (int)l,
+                          PolyArr{O, So, (l - 1) * N});
+            for (std::size_t k = 0; k < cnt; ++k) {
+                const std::size_t i = g.second[b0 + k];
+                scatter(c, out[i], O + k * So, So, l - 1, a[i]->scale * b[i]->scale / (double)c.q[l - 1]);
+            }
+        }
+    }
+}
+
+void sum_elems_many(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, uint64_t dim,
+                    const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    need(ctx != nullptr, "context is null");
+    if (B == 0) return;
+    need(x && out, "null argument");
+    set_device(ctx);
+    Ctx &c = ctx->c;
+    const std::vector<int> plan = LinalgPlan::sum_elems_steps(dim);
+    std::map<int, u32> elt_of;
+    for (uint64_t i = 0; i < B; ++i) {  // the schedule's first rotation on entry i, then (once) the others' keys
+        check_ct(ctx, x[i]);
+        check_obj(ctx, out[i], BAD_CT);
+        check_obj(ctx, gk, BAD_GK);
+        need(x[i]->size == 2, "encrypted size must be 2");
+        if (i == 0)
+            for (int st : plan) {  // powers of two: no NAF decomposition stands in for an absent key
+                const u32 e = elt_from_step(c, st);
+                need(gk->keys.count(e) > 0, "Galois key not present");
+                elt_of[st] = e;
+            }
+        need(dim == 1 || are_close(x[i]->scale, x[i]->scale), "scale mismatch");  // the adds' check
+    }
+    check_out_alias({x}, out, B);
+    const std::size_t N = c.N;
+    const auto groups = LinalgPlan::by_level(x, B);
+    std::size_t words = 0;
+    for (const auto &g : groups) {
+        const std::size_t l = g.first, Bc = linalg_chunk(c, l, g.second.size());
+        words = std::max(words, 4 * Bc * 2 * l * N + 2 * Bc * l * N + ks_words(c, Bc, l) + 8 * 64);
+    }
+    Scratch s(c, words);
+    for (const auto &g : groups) {
+        const std::size_t l = g.first, S0 = 2 * l * N, Bc = linalg_chunk(c, l, g.second.size());
+        s.top = 0;
+        u64 *slot[4];
+        for (u64 *&p : slot) p = s.take(Bc * S0);
+        for (std::size_t b0 = 0; b0 < g.second.size(); b0 += Bc) {
+            const int cnt = (int)std::min(Bc, g.second.size() - b0);
+            for (int k = 0; k < cnt; ++k) d2d(c, slot[0] + k * S0, x[g.second[b0 + k]]->d, S0);
+            // bvec (r), to_sum (t) and partial (p) as slots; a rotation writes a free slot (its reads gather, so it
+            // cannot run in place), an accumulate step reads its addend at the words it writes
+            bool used[4] = {true, false, false, false};
+            auto arr = [&](int i) { return PolyArr{slot[i], S0, l * N}; };
+            auto fresh = [&] {
+                for (int i = 0; i < 4; ++i)
+                    if (!used[i]) { used[i] = true; return i; }
+                throw std::logic_error("sum_elems: no free slot");
+            };
+            // dst = rotate(src, st) [+ add]
+            auto rot = [&](int src, int st, int add) {
+                const int dst = fresh();
+                const u32 e = elt_of.at(st);
+                galois_ks(c, s, arr(src), arr(dst), cnt, (int)l, e, gk->keys.at(e), add >= 0 ? arr(add) : PolyArr{});
+                return dst;
+            };
+            int r = 0, t = 0, p = -1;
+            bool have = false;
+            int window = 1;
+            if (dim & 1) {
+                have = true;
+                if (dim != 1) t = rot(t, window, -1);  // dim = 1: the reference discards this rotation
+            }
+            for (uint64_t bits = dim >> 1; bits != 0; bits >>= 1) {
+                window <<= 1;
+                if (!(bits & 1)) continue;
+                int steps = window >> 1;
+                int acc = rot(t, steps, t);  // acc = to_sum + (to_sum << steps)
+                if (!have && r != t) used[r] = false;
+                for (steps >>= 1; steps != 0; steps >>= 1) {  // acc += acc << steps
+                    const int n = rot(acc, steps, acc);
+                    used[acc] = false;
+                    acc = n;
+                }
+                if (have) {
+                    p = acc;
+                    ProfScope k(c, "k:k_ew_add/sum", 6.0 * cnt * l);
+                    ew_add(c, arr(r), arr(p), arr(r), cnt, 2, (int)l, 0);
+                    used[p] = false;
+                } else {
+                    r = acc;
+                    have = true;
+                }
+                if (bits != 1) {
+                    const int n = rot(t, window, -1);
+                    if (t != r) used[t] = false;
+                    t = n;
+                }
+            }
+            for (int k = 0; k < cnt; ++k) {
+                const std::size_t i = g.second[b0 + k];
+                scatter(c, out[i], slot[r] + k * S0, S0, l, x[i]->scale);
+            }
+        }
+    }
+}
+}  // namespace
+
+int hec_multiply_relin_rescale_many(hec_context *ctx, const hec_ciphertext *const *a, const hec_ciphertext *const *b,
+                                    uint64_t B, const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { product_many(ctx, a, b, B, rk, out); });
+}
+int hec_sum_elems_many(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, uint64_t dim,
+                       const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    return guard([&] { sum_elems_many(ctx, x, B, dim, gk, out); });
+}
+int hec_sum_elems_plan(uint64_t dim, int *steps, uint64_t cap, uint64_t *count)
+{
+    return guard([&] {
+        need(count != nullptr && (steps != nullptr || cap == 0), "null argument");
+        const std::vector<int> st = LinalgPlan::sum_elems_steps(dim);
+        *count = st.size();
+        for (std::size_t i = 0; i < st.size() && i < cap; ++i) steps[i] = st[i];
+    });
 }
 
 // ------------------------------------------------------------------ multi-GPU

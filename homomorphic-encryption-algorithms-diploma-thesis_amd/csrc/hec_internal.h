@@ -140,6 +140,9 @@ struct Ctx {
     bool kernel_memops = true;
     int prng_group = 0;            // option "prng_group": PRNG buffers per wavefront of k_prng (hec_keygen.hip), 1 .. 16;
                                    // 0 picks the largest that still fills the device.  Every value draws the same words
+    int rot_add = 1;               // option "rot_add": 1 a key switch's optional addend ADD (keyswitch() in hec_engine.hip) is
+                                   // added in its last stage (k_bmac's divide-and-round epilogue, k_moddown1); 0 by a
+                                   // k_ew_add launch after it.  Same words
     int math_chunk = 0;            // option "math_chunk": ciphertexts per pass of the he::math calls, 0 automatic (the
                                    // 65,535 y-blocks of an NTT launch bound it).  Every value computes the same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
@@ -179,14 +182,20 @@ void ks_mac(Ctx &c, PolyArr T, const u64 *E, const u64 *key, u64 *ACC, int B, in
 // special-prime target alone -> ACC[b][k][l]; tsel 2 the data targets, whose blocks run pass B of their chunks of the
 // rounding limbs Z (fan_divide_round's output) and store OUT = (acc - NTT(z)) P^-1 (+ IN through elt for polys
 // k < in_nk) instead of ACC.  A block reads IN only at the words it writes, so IN may be OUT.
+// BmacDRAdd: the same with a second addend ADD (both polys, unpermuted, read at the words the thread writes, so ADD
+// may be OUT): OUT = (acc - NTT(z)) P^-1 + perm(IN) + ADD, the rotate-and-accumulate step of a sum over slots.  Its
+// own type, so that the launches without ADD keep their instantiations
 struct BmacDR {
     const u64 *Z;
     PolyArr IN, OUT;
     int in_nk;
     u64 inv[HEC_MAXL], inv_q[HEC_MAXL];  // P^-1 mod q_i and its Shoup quotient
 };
+struct BmacDRAdd : BmacDR {
+    PolyArr ADD;
+};
 void ks_modup_mac(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l, int part,
-                  u32 elt, const BmacDR *dr = nullptr, int tsel = 0);
+                  u32 elt, const BmacDR *dr = nullptr, int tsel = 0, const PolyArr *add = nullptr);
 // divide-and-round by `last_idx` prime: Y = coefficient-form last limb per (b,k) (address Y + b*ysb + k*ysk),
 // X / IN / OUT addressed (b,k,i), nk polys per batch entry, nl output limbs.
 //   OUT = IN + (X - NTT(corr)) * inv   (IN optional; inv = last^-1 mod q_i)
@@ -238,9 +247,9 @@ void hoisted_mac_group(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *
 int hoisted_group(const Ctx &c);  // children per hoisted_mac_multi call for c.hmac_cfg
 void fan_divide_round(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, u64 *Z, int B, int nk, int nl, int last_idx);
 // the single-pass mod-down (hec_moddown1.hip): Y the coefficient-form special-prime limbs, X the ACC data limbs;
-// false when it does not apply (N != 2^15)
+// false when it does not apply (N != 2^15).  ADD (optional): a second addend of every poly, unpermuted (may be OUT)
 bool moddown1(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, PolyArr X, PolyArr IN, int in_nk, PolyArr OUT, int B, int nk,
-              int nl, int last_idx, u32 elt);
+              int nl, int last_idx, u32 elt, PolyArr ADD = PolyArr{});
 void galois_permute(Ctx &c, PolyArr in, PolyArr out, int B, int nk, int nl, u32 elt);
 void tensor_acc(Ctx &c, PolyArr R, const u64 *A, u64 a_sk, PolyArr ACC, int B, int l, bool assign);
 // deferred tensor products: ACC[b] (=|+=) sum_t R_t[b] (x) A_t, T <= TB_MAX rotated inputs

@@ -3028,6 +3028,7 @@ struct BmacDRB {
     const u64 *z[2], *in[2];
     u64 *out[2];
     u64 w, wq;
+    const u64 *add[2];  // ADD instantiations only
 };
 
 // SPL (integer targets): the pass-B butterflies as split-input Shoup, their extra twiddle words staged in ltwa
@@ -3035,7 +3036,10 @@ struct BmacDRB {
 // mod-down's rounding limbs Z (the same chunks, twiddles and rounds as a digit tile) and stores
 // OUT = (acc - NTT(z)) P^-1 (+ IN), what the divide-and-round pass B computes from ACC: the same exact arithmetic on
 // canonical residues, so the same words.  IN is read only at the words the thread writes (IN may be OUT).
-template <int LOGP, int NSEG, int EPT, bool FP, bool SPL = false, bool DR = false>
+// ADD (with DR): a second addend per poly, dr.add[k], read unpermuted at the words the thread writes (ADD may be OUT):
+// OUT = (acc - NTT(z)) P^-1 + perm(IN) + ADD, a rotate-and-accumulate step without its k_ew_add launch (which would
+// read two ciphertexts and write one).  Without ADD the body is the code it was.
+template <int LOGP, int NSEG, int EPT, bool FP, bool SPL = false, bool DR = false, bool ADD = false>
 __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr T, const u64 *__restrict__ E,
                                           const u64 *__restrict__ key,
                                           u64 *__restrict__ ACC, const TwTables &tt, const DevPrime &pr, int I, int kI,
@@ -3235,6 +3239,15 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
             u64 v[EPT];
             if constexpr (!FP && SPL) rounds(twgs, v);
             else rounds(twg0, v);
+            u64 ad[EPT];
+            if constexpr (ADD) {  // after the rounds: they hold the register peak
+#pragma unroll
+                for (int e = 0; e < EPT; e += 2) {
+                    const ulonglong2 w = *(const ulonglong2 *)(dr.add[k] + g0 + e);
+                    ad[e] = w.x;
+                    ad[e + 1] = w.y;
+                }
+            }
             u64 r[EPT];
 #pragma unroll
             for (int e = 0; e < EPT; ++e) {
@@ -3242,12 +3255,16 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
                     const double x = fp_reduce(acc[e], pr.qd, pr.qinv);
                     double y = fp_mulmod(x - __longlong_as_double((long long)v[e]), u2d(dr.w), pr.qd, pr.qinv);
                     if (ip) y += u2d(in[e]);
+                    // ADD: fp_mulmod leaves [-0.53q, 0.53q], IN and ADD are canonical residues, so y is an integer in
+                    // (-0.53q, 2.53q), below 2^44: exact, and within fp_canon's domain without a reduction in between
+                    if constexpr (ADD) y += u2d(ad[e]);
                     r[e] = fp_canon(y, pr.qd, pr.qinv);
                 } else {
                     const u64 x = barrett128(acc[e].lo, acc[e].hi, pr.q, pr.r0, pr.r1);
                     const u64 z = csub(csub(v[e], two_q), pr.q);
                     r[e] = shoup(x + pr.q - z, dr.w, dr.wq, pr.q);
                     if (ip) r[e] = addmod(r[e], in[e], pr.q);
+                    if constexpr (ADD) r[e] = addmod(r[e], ad[e], pr.q);
                 }
             }
 #pragma unroll
@@ -3305,7 +3322,8 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SI
     const int kI = I == l ? K - 1 : I;
     const DevPrime pr = primes[kI];
     if constexpr (sizeof...(DRA) == 1) {
-        const BmacDR &d = (dra, ...);
+        const auto &d = (dra, ...);
+        constexpr bool ADD = std::is_same_v<std::decay_t<decltype(d)>, BmacDRAdd>;
         BmacDRB db;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -3313,15 +3331,16 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SI
             db.z[k] = d.Z + ((u64)((b * 2 + k) * l + I) << logN);
             db.in[k] = (d.IN.p && k < d.in_nk) ? d.IN.p + b * d.IN.sb + k * d.IN.sk + li : nullptr;
             db.out[k] = d.OUT.p + b * d.OUT.sb + k * d.OUT.sk + li;
+            if constexpr (ADD) db.add[k] = d.ADD.p + b * d.ADD.sb + k * d.ADD.sk + li;
         }
         db.w = d.inv[I];
         db.wq = d.inv_q[I];
         if (yi < nint)
-            bmac_body<LOGP, NSEG, EPT, false, SPL, true>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l, K,
-                                                         elt, db);
+            bmac_body<LOGP, NSEG, EPT, false, SPL, true, ADD>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l,
+                                                              K, elt, db);
         else
-            bmac_body<LOGP, NSEG, EPT, true, false, true>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l,
-                                                          K, elt, db);
+            bmac_body<LOGP, NSEG, EPT, true, false, true, ADD>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN,
+                                                               l, K, elt, db);
     } else if (yi < nint)
         bmac_body<LOGP, NSEG, EPT, false, SPL>(lds, ltw, ltwa, T, E, key, ACC, tt, pr, I, kI, b, xb, logN, l, K, elt);
     else
@@ -3332,7 +3351,7 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / EPT, 4)  // 4 waves per SI
 // 200 VGPRs, 2 waves/SIMD) measured 1,062 vs 951 ms per step at cfg3 (round 3, gpurun_out/r03s)
 template <int LOGR, int LOGC, int NA, int NB2, int EPT = 4>
 static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l,
-                            int part, u32 elt, const BmacDR *dr, int tsel)
+                            int part, u32 elt, const BmacDR *dr, int tsel, const PolyArr *add)
 {
     constexpr int R = 1 << LOGR, C = 1 << LOGC;
     const TwTables fwd{c.tw, c.twb, c.twf, c.twbf, c.tws, c.twbs};
@@ -3356,7 +3375,13 @@ static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *
     const int gpad = (X * nI + 7) / 8 * 8;
     auto launch = [&](auto spl) {
         constexpr bool SPL = decltype(spl)::value;
-        if (tsel == 2)
+        if (tsel == 2 && add) {
+            BmacDRAdd da{};
+            static_cast<BmacDR &>(da) = *dr;
+            da.ADD = *add;
+            k_bmac<LOGC, NB2, EPT, SPL, BmacDRAdd><<<dim3(gpad * B), TB, 0, c.stream>>>(
+                T, E, key, ACC, fwd, c.primes, dm, nI, c.logN, l, (int)c.K, nint, gpad, elt, da);
+        } else if (tsel == 2)
             k_bmac<LOGC, NB2, EPT, SPL, BmacDR><<<dim3(gpad * B), TB, 0, c.stream>>>(
                 T, E, key, ACC, fwd, c.primes, dm, nI, c.logN, l, (int)c.K, nint, gpad, elt, *dr);
         else
@@ -3369,20 +3394,21 @@ static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *
 }
 
 void ks_modup_mac(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *key, u64 *ACC, int B, int l, int part,
-                  u32 elt, const BmacDR *dr, int tsel)
+                  u32 elt, const BmacDR *dr, int tsel, const PolyArr *add)
 {
     if ((tsel == 2) != (dr != nullptr) || tsel < 0 || tsel > 2) throw std::logic_error("ks_modup_mac: target selection");
+    if (add && !dr) throw std::logic_error("ks_modup_mac: an addend needs the divide-and-round epilogue");
     // <LOGR, LOGC, pass-A columns per block, fused pass-B chunks per block>: k_bmac blocks of 64-128
     // threads (4 chunks at N = 2^15: 110 us per B = 8 call vs 128 / 166 us at 16 / 32 chunks) keep the
     // serial digit loop of the slow integer-prime blocks short
     switch (c.logN) {
-    case 10: run_modup_fused<5, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 11: run_modup_fused<6, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 12: run_modup_fused<6, 6, 64, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 13: run_modup_fused<7, 6, 32, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 14: run_modup_fused<7, 7, 32, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 15: run_modup_fused<8, 7, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
-    case 16: run_modup_fused<8, 8, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel); break;
+    case 10: run_modup_fused<5, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 11: run_modup_fused<6, 5, 32, 16>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 12: run_modup_fused<6, 6, 64, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 13: run_modup_fused<7, 6, 32, 8>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 14: run_modup_fused<7, 7, 32, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 15: run_modup_fused<8, 7, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
+    case 16: run_modup_fused<8, 8, 16, 4>(c, D, E, T, key, ACC, B, l, part, elt, dr, tsel, add); break;
     default: throw std::invalid_argument("poly_modulus_degree must be 2^10 .. 2^16");
     }
 }

@@ -116,8 +116,11 @@ struct MD1Args {
     u64 inv[HEC_MAXL], inv_q[HEC_MAXL];
 };
 
-template <bool FP>
-__device__ __forceinline__ void md1_body(const MD1Args &A, u64 *lds, const DevPrime &pr, const void *tw, int g, int i)
+// ADD: a second addend, both polys, read unpermuted at the words the thread writes (so it may be OUT): the
+// rotate-and-accumulate step OUT = (ACC - NTT(r)) P^-1 + perm(IN) + ADD of a sum over slots in one store
+template <bool FP, bool ADD>
+__device__ __forceinline__ void md1_body(const MD1Args &A, u64 *lds, const DevPrime &pr, const void *tw, int g, int i,
+                                         const PolyArr &add)
 {
     const int t = threadIdx.x, a = t >> 5, b = t & 31;
     const int bb = g / A.nk, k = g % A.nk;
@@ -155,10 +158,14 @@ __device__ __forceinline__ void md1_body(const MD1Args &A, u64 *lds, const DevPr
     u64 *out = A.OUT.p + (u64)bb * A.OUT.sb + (u64)k * A.OUT.sk + li;
     const u64 *in = (A.IN.p != nullptr && k < A.in_nk) ? A.IN.p + (u64)bb * A.IN.sb + (u64)k * A.IN.sk + li : nullptr;
     const u64 w = A.inv[i], wq = A.inv_q[i];
+    const u64 *ad = nullptr;
+    if constexpr (ADD) ad = add.p + (u64)bb * add.sb + (u64)k * add.sk + li;
 #pragma unroll
     for (int l = 0; l < 32; l += 2) {
         const u64 o = o0 + l;
         const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(xa + o);
+        ulonglong2 av{0, 0};
+        if constexpr (ADD) av = *reinterpret_cast<const ulonglong2 *>(ad + o);
         ulonglong2 iv{0, 0};
         if (in) {
             if (A.elt == 1) {
@@ -176,11 +183,15 @@ __device__ __forceinline__ void md1_body(const MD1Args &A, u64 *lds, const DevPr
             if constexpr (FP) {
                 double d = fp_mulmod(u2d(xv) - __longlong_as_double((long long)v[l + e]), u2d(w), pr.qd, pr.qinv);
                 if (in) d += u2d(inv_);
+                // ADD: fp_mulmod leaves [-0.53q, 0.53q], IN and ADD are canonical residues, so d is an integer in
+                // (-0.53q, 2.53q), below 2^44: exact, and within fp_canon's domain without a reduction in between
+                if constexpr (ADD) d += u2d(e ? av.y : av.x);
                 r[e] = fp_canon(d, pr.qd, pr.qinv);
             } else {
                 const u64 vv = csub(csub(v[l + e], 2 * pr.q), pr.q);
                 u64 s = shoup(xv + pr.q - vv, w, wq, pr.q);
                 if (in) s = addmod(s, inv_, pr.q);
+                if constexpr (ADD) s = addmod(s, e ? av.y : av.x, pr.q);
                 r[e] = s;
             }
         }
@@ -191,23 +202,24 @@ __device__ __forceinline__ void md1_body(const MD1Args &A, u64 *lds, const DevPr
 // One arithmetic class per launch (each keeps its own 128-VGPR budget: 16 waves per CU).  XCD-aware order: the nt
 // targets of one (b, k) run back to back on one XCD (blocks x, x + 8, ...), so the source limb y comes from HBM for
 // the first and from that XCD's L2 for the others
-template <bool FP>
+template <bool FP, bool ADD = false>
 __global__ void __launch_bounds__(1024) k_moddown1(const MD1Args A, const u64 *__restrict__ twi,
-                                                   const double *__restrict__ twf, const DevPrime *__restrict__ primes)
+                                                   const double *__restrict__ twf, const DevPrime *__restrict__ primes,
+                                                   const PolyArr add)
 {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     const int x = blockIdx.x, xcd = x & 7, tq = x >> 3;
     const int g = (tq / A.nt) * 8 + xcd, i = A.ti[tq % A.nt];
     if (g >= A.B * A.nk) return;  // uniform per block
     const DevPrime pr = primes[i];
-    if constexpr (FP) md1_body<true>(A, lds, pr, twf + ((u64)i << kLogN), g, i);
-    else md1_body<false>(A, lds, pr, twi + ((u64)i << (kLogN + 1)), g, i);
+    if constexpr (FP) md1_body<true, ADD>(A, lds, pr, twf + ((u64)i << kLogN), g, i, add);
+    else md1_body<false, ADD>(A, lds, pr, twi + ((u64)i << (kLogN + 1)), g, i, add);
 }
 
 }  // namespace
 
 bool moddown1(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, PolyArr X, PolyArr IN, int in_nk, PolyArr OUT, int B, int nk,
-              int nl, int last_idx, u32 elt)
+              int nl, int last_idx, u32 elt, PolyArr ADD)
 {
     if (c.logN != kLogN || B <= 0 || nl <= 0 || nl > HEC_MAXL) return false;
     MD1Args A{};
@@ -228,6 +240,10 @@ bool moddown1(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, PolyArr X, PolyArr IN, int
                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         HEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_moddown1<false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        HEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_moddown1<true, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        HEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_moddown1<false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     });
     const unsigned groups = (unsigned)((B * nk + 7) / 8 * 8);
     for (int fp = 0; fp < 2; ++fp) {  // the integer targets first (fewer, slower blocks start early)
@@ -235,12 +251,12 @@ bool moddown1(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, PolyArr X, PolyArr IN, int
         for (int i = 0; i < nl; ++i)
             if ((c.hprimes[i].fp != 0) == (fp != 0)) A.ti[A.nt++] = i;
         if (A.nt == 0) continue;
-        if (fp)
-            k_moddown1<true><<<dim3(groups * (unsigned)A.nt), 1024, bytes, c.stream>>>(
-                A, reinterpret_cast<const u64 *>(c.tw), c.twf, c.primes);
-        else
-            k_moddown1<false><<<dim3(groups * (unsigned)A.nt), 1024, bytes, c.stream>>>(
-                A, reinterpret_cast<const u64 *>(c.tw), c.twf, c.primes);
+        const dim3 grid(groups * (unsigned)A.nt);
+        const u64 *twi = reinterpret_cast<const u64 *>(c.tw);
+        if (fp && ADD.p) k_moddown1<true, true><<<grid, 1024, bytes, c.stream>>>(A, twi, c.twf, c.primes, ADD);
+        else if (fp) k_moddown1<true><<<grid, 1024, bytes, c.stream>>>(A, twi, c.twf, c.primes, ADD);
+        else if (ADD.p) k_moddown1<false, true><<<grid, 1024, bytes, c.stream>>>(A, twi, c.twf, c.primes, ADD);
+        else k_moddown1<false><<<grid, 1024, bytes, c.stream>>>(A, twi, c.twf, c.primes, ADD);
         HEC_HIP(hipGetLastError());
     }
     return true;

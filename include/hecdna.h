@@ -86,8 +86,10 @@ int hec_context_synchronize(hec_context *ctx);
  * bit-identical.  Applies to the context and its batch lanes; HEC_EINVAL for an unknown name, and for a value
  * outside an enumerated knob's range ("split_bfly" 0..4, "hmac" 0..2, "hmac_odd3" 0..1, "hoist_scan" 0..1,
  * "nttb_shfl" 0..2, "nttb_shfl_dr" 0..1, "moddown1" 0..1, "hmac_int" 0..1, "nt_e" 0..1,
- * "mac_divround" 0..1, "prng_group" 0..16).  "math_chunk" (0..65535) caps the ciphertexts per pass of the he::math
- * calls below; 0 is automatic, a negative value HEC_EINVAL. */
+ * "mac_divround" 0..1, "prng_group" 0..16, "rot_add" 0..1).  "math_chunk" (0..65535) caps the ciphertexts per pass
+ * of the he::math calls and of hec_multiply_relin_rescale_many / hec_sum_elems_many below; 0 is automatic, a negative
+ * value HEC_EINVAL.  "rot_add": 1 the rotate-and-accumulate steps of hec_sum_elems_many add the accumulator in the
+ * key switch's last stage (k_bmac's divide-and-round epilogue, k_moddown1), 0 in a k_ew_add launch after it. */
 int hec_context_set_option(hec_context *ctx, const char *name, int64_t value);
 uint64_t hec_context_poly_degree(const hec_context *ctx);
 uint64_t hec_context_key_moduli(const hec_context *ctx); /* K */
@@ -359,6 +361,34 @@ int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, d
 /* he::util::drop_chain_levels (he_util.h:27-48) on B ciphertexts in place: per level, every ciphertext times the
  * scalar encode of 1 at the first one's level and scale, rescaled.  Inputs and errors as above; levels = 0 is a no-op */
 int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels);
+
+/* ---------------------------------------------------------------- he::linalg element-wise products and sums */
+/* The members of he::linalg that touch many ciphertexts element by element (Matrix::operator*=, BatchedMatrix::
+ * operator*=, square_inplace and sum_bvec_elems_inplace) as single calls over B ciphertexts: out[i] is, word for word
+ * and with the same level and scale, what the per-operation calls give for entry i alone.  Entries may sit at
+ * different levels and scales: they are grouped by level on the host, each group runs its stages over the whole group
+ * (in passes of at most 65,535 / ((l + 1) l) ciphertexts, or the option "math_chunk"), and the outputs keep the
+ * caller's order.  Every check runs before anything is written, in entry order, and the status and message are those
+ * of the per-operation call on the lowest failing entry: inputs of size 2 ("encrypted size must be 2"), "encrypted1
+ * and encrypted2 parameter mismatch" for a pair at two levels, "scale out of bounds", "end of modulus switching chain
+ * reached", "Galois key not present", the messages of a key or ciphertext of another context.  out[i] may be a fresh
+ * handle or entry i's own input; an output handle that is another entry's input, or that appears twice, is
+ * HEC_EINVAL ("an output may alias only its own entry's inputs").  B = 0 succeeds and does nothing.  Ordered on the
+ * context's stream. */
+/* out[i] = rescale_to_next(relinearize(a[i] * b[i], rk)); b[i] == a[i] (the same handle) is square. */
+int hec_multiply_relin_rescale_many(hec_context *ctx, const hec_ciphertext *const *a,
+                                    const hec_ciphertext *const *b, uint64_t B,
+                                    const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* out[i] = BatchedVector::sum_elems_inplace on x[i] with this dim (he_linalg.cpp:667-713): slot 0 of every block of
+ * dim slots holds the block's sum.  gk must hold the key of every step of hec_sum_elems_plan(dim); dim = 0 is
+ * HEC_EINVAL ("dim must be positive").  With the option "rot_add" = 1 every accumulate step acc + rotate(src, step)
+ * is one key switch whose last stage also adds acc; with 0 the add is a launch of its own.  Same words either way. */
+int hec_sum_elems_many(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, uint64_t dim,
+                       const hec_galois_keys *gk, hec_ciphertext *const *out);
+/* host only: the rotation steps that schedule issues for dim, in order, including the ones whose
+ * result the reference discards (e.g. dim = 1 rotates once and keeps the input).  *count is their number; at most
+ * cap of them are written to steps (steps may be null when cap is 0). */
+int hec_sum_elems_plan(uint64_t dim, int *steps, uint64_t cap, uint64_t *count);
 
 /* ---------------------------------------------------------------- multi-GPU (SURVEY 8(b),(e)) */
 /* One process per GPU.  The reference is single-threaded (no collective anywhere); the sharded matvec splits
