@@ -987,6 +987,55 @@ void walk_trie_hoisted(Ctx &c, Scratch &s, const RotTrie &t, int node, PolyArr s
                                  galois_kw(ctx, gk, e, l), fold ? galois_mkey(ctx, gk, e) : nullptr};
         }
         const double K = l + 1;  // per child: key (2 l K), W (K), KW (2 K), ACC (2 B K)
+        // hmac_divround: the group launch (hmac_cfg 2, so ng <= HOIST_GROUP is one launch and the node's c0 is folded:
+        // no IN term) in the order of the per-rotation mac_divround: the special-prime target of every child, its INTT
+        // and the fan-out over the group, then the data targets' launch divides-and-rounds its accumulators into the
+        // children's rotation buffers.  Short of rotation buffers for the group: the unfolded path below
+        if (c.hmac_divround && c.hmac_cfg == 2 && c.hmac_int && c.fan_out && !(c.moddown1 && c.logN == 15) &&
+            (int)bufs.b[depth + 1].size() >= ng) {
+            const PolyArr X1{src.p + src.sk, src.sb, 0};
+            PolyArr dst[HOIST_GROUP];
+            HChildSpec outs[HOIST_GROUP];
+            for (int q = 0; q < ng; ++q) {  // taken before the data launch writes them
+                dst[q] = PolyArr{bufs.take(depth + 1), stride, (u64)l * N};
+                before_write(dst[q].p);
+                outs[q] = kids[q];
+                outs[q].ACC = dst[q].p;
+            }
+            const std::size_t top = s.top;
+            const u64 sz = (u64)B * 2 * l * N;
+            u64 *Z = s.take((u64)ng * sz);
+            {  // digits E[b][P] (B l) + per child key (2 l), W, KW (3) -> ACC's P limbs (2 B)
+                ProfScope ps(c, "ks_hmac");
+                ProfScope k(c, "k:k_hmacm/p", (double)B * l + ng * (2.0 * l + 3.0 + 2.0 * B));
+                hoisted_mac_group(c, X1, X0, h.E, h.zl, kids, ng, B, l, 1);
+            }
+            {
+                ProfScope ps(c, "ks_moddown");
+                const int pP[1] = {(int)c.K - 1};
+                {
+                    ProfScope k(c, "k:k_ntt/moddown_intt", 4.0 * B * ng);
+                    ntt_strided(c, true, h.acc(0) + l * N, (l + 1) * N, h.acc(0) + l * N, (l + 1) * N, 1, pP, 2 * B * ng, 1,
+                                1);
+                }
+                ProfScope k(c, "k:k_fan2/moddown", 2.0 * B * ng * (l + 1));
+                fan_divide_round(c, h.acc(0) + l * N, 2 * (l + 1) * N, (l + 1) * N, Z, B * ng, 2, l, (int)c.K - 1);
+            }
+            {  // digits E (B l (l - 1)) + c1, c0 (2 B l) + per child key (2 l l), W, KW (3 l), Z (2 B l) -> OUT (2 B l)
+                ProfScope ps(c, "ks_hmac");
+                ProfScope k(c, "k:k_hmacm/divround",
+                            (double)B * (l * l + 2 * l) - (double)B * l + ng * (2.0 * l * l + 3.0 * l + 4.0 * B * l));
+                HmacDR dr{};
+                dr.Z = Z; dr.zs = sz; dr.osb = stride; dr.osk = (u64)l * N; dr.twb = c.twb; dr.twbf = c.twbf;
+                for (int i = 0; i < l; ++i) { dr.inv[i] = c.p_inv[i]; dr.inv_q[i] = c.p_inv_q[i]; }
+                hoisted_mac_group(c, X1, X0, h.E, h.zl, outs, ng, B, l, 2, &dr);
+            }
+            s.top = top;
+            for (int q = 0; q < ng; ++q)
+                walk_trie_hoisted(c, s, t, ch[g0 + q], dst[q], depth + 1, B, l, ctx, gk, bufs, hs, stride, min_children,
+                                  visit, before_write);
+            continue;
+        }
         for (int q0 = 0, nk = 0; q0 < ng; q0 += nk) {  // one profile scope per launch (bench.py's roofline)
             nk = std::min((int)grp, ng - q0);
             // an odd group's last three children as one 3-child launch (the digits read once, not twice)
@@ -1633,11 +1682,19 @@ int hec_context_create(uint64_t N, const uint64_t *mod, uint64_t K, int device, 
             need(end != f && *end == 0 && v >= 0 && v <= 1, "HEC_MAC_DIVROUND takes 0..1");
             mac_divround = (int)v;
         }
+        int hmac_divround = -1;
+        if (const char *f = std::getenv("HEC_HMAC_DIVROUND")) {
+            char *end = nullptr;
+            const long v = std::strtol(f, &end, 10);
+            need(end != f && *end == 0 && v >= 0 && v <= 1, "HEC_HMAC_DIVROUND takes 0..1");
+            hmac_divround = (int)v;
+        }
         HEC_HIP(hipSetDevice(device));
         auto *ctx = new hec_context();
         Ctx &c = ctx->c;
         c.device = device;
         if (mac_divround >= 0) c.mac_divround = mac_divround;
+        if (hmac_divround >= 0) c.hmac_divround = hmac_divround;
         if (const char *f = std::getenv("HEC_FUSED_MODUP_MAC")) c.fused_modup_mac = f[0] != '0';
         if (const char *f = std::getenv("HEC_FUSE_GALOIS")) c.fuse_galois = f[0] != '0';
         if (const char *f = std::getenv("HEC_FAN")) c.fan_out = f[0] != '0';
@@ -1900,6 +1957,7 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "nt_e") c.nt_e = in(0, 1);
             else if (n == "bmac_split") c.bmac_split = value != 0;
             else if (n == "mac_divround") c.mac_divround = in(0, 1);
+            else if (n == "hmac_divround") c.hmac_divround = in(0, 1);
             else if (n == "hoist") c.hoist = value != 0;
             else if (n == "hoist_min") c.hoist_min_children = (int)std::max<int64_t>(1, value);
             else if (n == "hmac") c.hmac_cfg = in(0, 2);

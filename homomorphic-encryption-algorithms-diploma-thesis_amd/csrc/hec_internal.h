@@ -91,6 +91,12 @@ struct Ctx {
     // accumulators in an epilogue (no ACC data limbs in memory, no divide-and-round pass B launch); 0 the separate
     // pass B.  Applies with fan_out && fused_modup_mac && !moddown1
     int mac_divround = 1;
+    // HEC_HMAC_DIVROUND / option "hmac_divround": 1 the same order for the children of a hoisted node: per sibling
+    // group k_hmacm accumulates the special-prime target alone, the P-limb INTT and the fan-out give every child's
+    // rounding limbs, and the data targets' k_hmacm launch divides-and-rounds its accumulators in an epilogue,
+    // straight into the children's rotation buffers; 0 the accumulators go to memory and k_ntt's pass B reads them
+    // back.  Applies to the group launch (hmac_cfg 2, hmac_int 1) with fan_out && !moddown1 and enough rotation buffers
+    int hmac_divround = 1;
     // hoisted mod-up (see hec_kernels.hip): psi_i^e for e in [0, 2N) per key prime, c[J][I] = q_J mod q_I,
     // and a device flag raised when a digit limb holds more zero coefficients than the kernels correct
     u64 *psipow = nullptr;
@@ -242,8 +248,20 @@ void hoisted_mac_multi(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *
 // three children in one sibling-fused launch (3 x 4 FP64 / 3 x 2 integer batch entries per thread)
 void hoisted_mac_3(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *zl, const HChildSpec *kids, int B, int l);
 // a whole sibling group (up to HMAC_MAX_CHILDREN) in one launch: slots of 2 children, the digit tile shared through L2
+// dr == nullptr, tsel 0: every target I in [0, l] -> ACC.  tsel 1: the special-prime target alone -> ACC[b][k][l].
+// tsel 2 (with dr): the data targets, whose blocks run pass B of their children's chunks of the rounding limbs Z
+// (fan_divide_round's output over the group, child q at Z + q zs) and store (acc - NTT(z)) P^-1 instead of ACC: the
+// child's HChildSpec::ACC is then its output ciphertext (entry b, poly k at ACC + b osb + k osk).  The zero
+// corrections follow each launch; at tsel 2 they are applied to the outputs, times P^-1
+struct HmacDR {
+    const u64 *Z;
+    u64 zs, osb, osk;
+    const ulonglong2 *twb;  // pass-B twiddle tables (Ctx::twb / twbf)
+    const double *twbf;
+    u64 inv[HEC_MAXL], inv_q[HEC_MAXL];  // P^-1 mod q_i and its Shoup quotient
+};
 void hoisted_mac_group(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *zl, const HChildSpec *kids, int nkids,
-                       int B, int l);
+                       int B, int l, int tsel = 0, const HmacDR *dr = nullptr);
 int hoisted_group(const Ctx &c);  // children per hoisted_mac_multi call for c.hmac_cfg
 void fan_divide_round(Ctx &c, const u64 *Y, u64 ysb, u64 ysk, u64 *Z, int B, int nk, int nl, int last_idx);
 // the single-pass mod-down (hec_moddown1.hip): Y the coefficient-form special-prime limbs, X the ACC data limbs;

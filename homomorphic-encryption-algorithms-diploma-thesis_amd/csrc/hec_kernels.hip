@@ -27,28 +27,18 @@ __device__ __forceinline__ ulonglong2 ld2(const u64 *p, u64 g)
     const u64x2 w = *reinterpret_cast<const u64x2 *>(p + g);
     return make_ulonglong2(w.x, w.y);
 }
-// Non-temporal stores for the step's large streaming intermediates (round 6): each is written once and read by a
-// later kernel, and none fits the caches (GB per launch), so keeping their lines only delays write-back into the next
-// kernel's time.  Bits of HEC_NT_MASK: 1 the fan-outs' target tiles (Z, mod-up pass-A tiles), 2 the divide-and-round
-// output, 4 the hoisted MAC's accumulators; the hoisted digits E are Ctx::nt_e (ModUpIO_BT).
-#ifndef HEC_NT_MASK
-#define HEC_NT_MASK 0
-#endif
-constexpr int kNtMask = HEC_NT_MASK;
-template <int BIT>
-__device__ __forceinline__ void st1m(u64 *p, u64 v)
-{
-    if constexpr ((kNtMask & BIT) != 0) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-template <int BIT>
-__device__ __forceinline__ void st2m(u64 *p, ulonglong2 v)
+// Non-temporal stores for the step's large streaming intermediates: each is written once and read by a later kernel,
+// and none fits the caches (GB per launch), so keeping their lines only delays write-back into the next kernel's time.
+// Settled by A/B: the hoisted digits E (Ctx::nt_e, ModUpIO_BT) and the fan-outs' target tiles (Z, the
+// mod-up pass-A tiles) are stored non-temporally; the divide-and-round outputs and the hoisted MAC's accumulators
+// keep the default policy.
+__device__ __forceinline__ void st1_nt(u64 *p, u64 v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void st2v(u64 *p, ulonglong2 v)
 {
     u64x2 w;
     w.x = v.x;
     w.y = v.y;
-    if constexpr ((kNtMask & BIT) != 0) __builtin_nontemporal_store(w, reinterpret_cast<u64x2 *>(p));
-    else *reinterpret_cast<u64x2 *>(p) = w;
+    *reinterpret_cast<u64x2 *>(p) = w;
 }
 // a non-temporal 16-B store (the nt cache policy: the line is not kept for reuse)
 __device__ __forceinline__ void st2_nt(u64 *p, u64 g, u64 a, u64 b)
@@ -282,7 +272,7 @@ struct DivRoundIOB {
         {
             u64 r = shoup(p.x + q - v, w, wq, q);
             if (HAS_IN && in) r = addmod(r, p.in, q);
-            st1m<2>(out + g, r);
+            out[g] = r;
         }
         // v: the FP64 NTT output before canonicalisation (|v| < 10 q): (x - v) P^-1 (+ in) with one exact
         // fp_mulmod (|x - v| < 11 q) and one canonicalisation, instead of Shoup on u64 plus fp_canon
@@ -290,7 +280,7 @@ struct DivRoundIOB {
         {
             double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv);
             if (HAS_IN && in) r += u2d(p.in);
-            st1m<2>(out + g, fp_canon(r, pr.qd, pr.qinv));
+            out[g] = fp_canon(r, pr.qd, pr.qinv);
         }
     };
     __device__ Bound bind(int job) const
@@ -384,12 +374,12 @@ struct FftIOB {
         }
         __device__ void store(u64 g, u64 v, Pre p) const
         {
-            st1m<2>(out + g, shoup(p.x + pr.q - v, w, wq, pr.q));
+            out[g] = shoup(p.x + pr.q - v, w, wq, pr.q);
         }
         __device__ void store_fp(u64 g, double v, Pre p, const DevPrime &) const
         {
             const double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv);
-            st1m<2>(out + g, fp_canon(r, pr.qd, pr.qinv));
+            out[g] = fp_canon(r, pr.qd, pr.qinv);
         }
     };
     __device__ Bound bind(int job) const
@@ -1341,13 +1331,13 @@ struct MathIOB {
         __device__ u64 load(u64 g) const { return z[g]; }
         __device__ void store(u64 g, u64 v, Pre p) const
         {
-            st1m<2>(out + g, addmod(shoup(p.x + pr.q - v, w, wq, pr.q), d, pr.q));
+            out[g] = addmod(shoup(p.x + pr.q - v, w, wq, pr.q), d, pr.q);
         }
         // |x - v| < 11 q as in DivRoundIOB; the product lies in [-0.53 q, 0.53 q], d in [0, q)
         __device__ void store_fp(u64 g, double v, Pre p, const DevPrime &) const
         {
             const double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv) + u2d(d);
-            st1m<2>(out + g, fp_canon(r, pr.qd, pr.qinv));
+            out[g] = fp_canon(r, pr.qd, pr.qinv);
         }
     };
     __device__ Bound bind(int job) const
@@ -1817,7 +1807,7 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / 16)
         else ntt_round_r<LOGP, 4, LOGP, false, false>(v, ts, tw, pt);
         // (16-B stores and loads through lane-pair trades measured slower: 2,613 vs 2,580 ms per step, round 4)
 #pragma unroll
-        for (int k = 0; k < 16; ++k) st1m<1>(tgt.out + gblock(k), v[k]);
+        for (int k = 0; k < 16; ++k) st1_nt(tgt.out + gblock(k), v[k]);
     }
 }
 
@@ -1964,7 +1954,7 @@ __global__ void __launch_bounds__(NSEG *(1 << LOGP) / 16, 2)  // 2 waves per SIM
             }
             // (16-B stores and loads through lane-pair trades measured slower: 2,613 vs 2,580 ms per step, round 4)
 #pragma unroll
-            for (int k = 0; k < 16; ++k) st1m<1>(tgt.out + gblock(k), v[k]);
+            for (int k = 0; k < 16; ++k) st1_nt(tgt.out + gblock(k), v[k]);
         }
         // a target slice [t0, t1) without a valid target for this job (gridDim.z > 1) loaded nothing above: the next
         // job's source still has to replace d (block-uniform, never taken with one target group)
@@ -2280,6 +2270,23 @@ struct HChildren {
 // and lost: k_hmacm 2,699-2,720 vs 2,501-2,540 ms per step at B = 128; the 60-bit targets keep the u64 loop.)
 __device__ __forceinline__ u64 mform(u64 v, bool fp) { return fp ? (u64)__double_as_longlong(u2d(v)) : v; }
 
+// The divide-and-round epilogue's operands of one k_hmacm block (HmacDR resolved per block): the rounding limbs of
+// the slot's first child, P^-1 mod q_I with its Shoup quotient, the pass-B twiddle tables at limb kI and the block's
+// LDS (two sets of 512 words, one twiddle row per chunk)
+struct HmacDRB {
+    const u64 *Z;
+    u64 zs, osb, osk, w, wq;
+    const ulonglong2 *tw;
+    const double *twf;
+    u64 *lds, *ltw;
+};
+// defined after the chunk rows and rounds of k_bmac, which it shares (hmac_divround)
+constexpr int bmac_ld(int logp);
+template <int LOGP, bool FP, int BT, int CG, class AccF>
+__device__ __forceinline__ void hmacm_divround(const HmacDRB &dr, const HChildren<CG> &ch, const u64 *kc,
+                                               const bool *sw, int B, int l, int logN, const DevPrime &pr, int I,
+                                               int b0, const AccF &acc);
+
 // The digit loop of k_hmacm at the FP64 targets on MAC-form operands (round 6).  The thread's two source positions
 // s0, s0 + 1 read the digit words E[b][I][J][s0..] and each child's key words MK_c[J][k][I][s0..] (mac_key_table:
 // key_c at gal_c(s) = galois_src(s, einv_c), so both streams are contiguous and in the same order, and no pair swap
@@ -2287,10 +2294,11 @@ __device__ __forceinline__ u64 mform(u64 v, bool fp) { return fp ? (u64)__double
 // store.  The loop is unrolled by two with explicit double buffers (digit J + 1's words load while digit J
 // multiplies), so no register is copied per digit; exact fp_mulmod products summed as doubles.  The J == I digit is
 // the child's own NTT-form c1 (canonical u64, converted once).  The zero corrections are k_hmacm_zfix's.
-template <int BT, int CG>
+// LOGP != 0 (hmac_divround, the data targets): no ACC store; hmacm_divround's epilogue on the reduced sums.
+template <int BT, int CG, int LOGP = 0>
 __device__ __forceinline__ void hmacm_body(PolyArr X1, PolyArr X0, const u64 *__restrict__ E, const HChildren<CG> &ch,
                                            int B, int l, int K, int logN, const DevPrime &pr, u64 Pq, int I, int kI,
-                                           u64 s0, int b0)
+                                           u64 s0, int b0, const HmacDRB &dr = HmacDRB{})
 {
     const u64 N = 1ull << logN;
     u64 kc[CG];         // even slot of child c's output pair
@@ -2422,6 +2430,12 @@ __device__ __forceinline__ void hmacm_body(PolyArr X1, PolyArr X0, const u64 *__
     } else if (k < nd) {
         mac(eA, kA);
     }
+    if constexpr (LOGP != 0) {  // the sums (|f| <= 0.53 q (l + 2)) reduced to [-0.53q, 0.53q], as k_bmac's epilogue
+        hmacm_divround<LOGP, true, BT, CG>(dr, ch, kc, sw, B, l, logN, pr, I, b0, [&](int q, int t, int i) {
+            return fp_reduce(f[q][t][i], pr.qd, pr.qinv);
+        });
+        return;
+    }
 #pragma unroll
     for (int q = 0; q < CG; ++q) {
         if (q >= ch.n) break;
@@ -2434,8 +2448,8 @@ __device__ __forceinline__ void hmacm_body(PolyArr X1, PolyArr X0, const u64 *__
             for (int i = 0; i < 4; ++i) r[i] = fp_canon(f[q][t][i], pr.qd, pr.qinv);
             u64 *o0 = ch.c[q].ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + kc[q];
             u64 *o1 = ch.c[q].ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + kc[q];
-            st2m<4>(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
-            st2m<4>(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
+            st2v(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
+            st2v(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
         }
     }
 }
@@ -2560,8 +2574,8 @@ __device__ __forceinline__ void hmacm_body_u64(PolyArr X1, PolyArr X0, const u64
             for (int i = 0; i < 4; ++i) r[i] = barrett128(a[q][t][i].lo, a[q][t][i].hi, pr.q, pr.r0, pr.r1);
             u64 *o0 = ch.c[q].ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + kc[q];
             u64 *o1 = ch.c[q].ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + kc[q];
-            st2m<4>(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
-            st2m<4>(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
+            st2v(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
+            st2v(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
         }
     }
 }
@@ -2569,10 +2583,10 @@ __device__ __forceinline__ void hmacm_body_u64(PolyArr X1, PolyArr X0, const u64
 // The 60-bit targets on the MAC-form streams (round 6): the FP64 body's loads (source-ordered key table MK, canonical
 // u64 at these limbs; buffer loads; the J == I digit before the loop; unconditional double-buffered loads) with SEAL's
 // 128-bit lazy sums, one Barrett reduction per output word.  HEC_HMAC_INT=0: the round-5 loop above.
-template <int BT, int CG>
+template <int BT, int CG, int LOGP = 0>
 __device__ __forceinline__ void hmacm_body_int(PolyArr X1, PolyArr X0, const u64 *__restrict__ E, const HChildren<CG> &ch,
                                                int B, int l, int K, int logN, const DevPrime &pr, u64 Pq, int I,
-                                               int kI, u64 s0, int b0)
+                                               int kI, u64 s0, int b0, const HmacDRB &dr = HmacDRB{})
 {
     const u64 N = 1ull << logN;
     u64 kc[CG];
@@ -2687,6 +2701,12 @@ __device__ __forceinline__ void hmacm_body_int(PolyArr X1, PolyArr X0, const u64
     } else if (k < nd) {
         mac(eA, kA);
     }
+    if constexpr (LOGP != 0) {
+        hmacm_divround<LOGP, false, BT, CG>(dr, ch, kc, sw, B, l, logN, pr, I, b0, [&](int q, int t, int i) {
+            return barrett128(a[q][t][i].lo, a[q][t][i].hi, pr.q, pr.r0, pr.r1);
+        });
+        return;
+    }
 #pragma unroll
     for (int q = 0; q < CG; ++q) {
         if (q >= ch.n) break;
@@ -2699,8 +2719,8 @@ __device__ __forceinline__ void hmacm_body_int(PolyArr X1, PolyArr X0, const u64
             for (int i = 0; i < 4; ++i) r[i] = barrett128(a[q][t][i].lo, a[q][t][i].hi, pr.q, pr.r0, pr.r1);
             u64 *o0 = ch.c[q].ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + kc[q];
             u64 *o1 = ch.c[q].ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + kc[q];
-            st2m<4>(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
-            st2m<4>(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
+            st2v(o0, sw[q] ? ulonglong2{r[1], r[0]} : ulonglong2{r[0], r[1]});
+            st2v(o1, sw[q] ? ulonglong2{r[3], r[2]} : ulonglong2{r[2], r[3]});
         }
     }
 }
@@ -2764,11 +2784,15 @@ struct HSlots {
 // of one (coefficient block, I, batch group) — the same digit tile E, the node's c1 / c0 words, different children —
 // are consecutive blocks of that XCD (ids w, w + 8, w + 16): the tile comes from HBM for the first and from the XCD's
 // L2 for the others, so the digits, the kernel's largest stream, cross HBM once per sibling group, not per pair.
-template <int BTF, int BTI, int CG, int MINW, int NS>
+// DRA = one HmacDR (hmac_divround): the data targets' launch with the divide-and-round epilogue at chunk size 2^LOGP
+// (Imap lists data primes only; the children's ACC fields are their output ciphertexts); no DRA: the accumulators go
+// to ACC
+template <int BTF, int BTI, int CG, int MINW, int NS, int LOGP = 0, class... DRA>
 __global__ void __launch_bounds__(256, MINW)  // MINW waves per SIMD: 3 -> <= 168 VGPRs, 2 -> <= 256
     k_hmacm(PolyArr X1, PolyArr X0, const u64 *__restrict__ E, const int *__restrict__ zl, const HSlots<CG, NS> S,
             int B, int l, int K, int logN, const DevPrime *__restrict__ primes, const int *__restrict__ Imap, int nI,
-            int nint, const u64 *__restrict__ cji, const u64 *__restrict__ psipow, int wsplit, int int_mform)
+            int nint, const u64 *__restrict__ cji, const u64 *__restrict__ psipow, int wsplit, int int_mform,
+            const DRA... dra)
 {
     const u64 N = 1ull << logN;
     const int X = (int)(N / 512);
@@ -2788,7 +2812,17 @@ __global__ void __launch_bounds__(256, MINW)  // MINW waves per SIMD: 3 -> <= 16
     const DevPrime pr = primes[kI];
     const u64 s0 = (u64)xb * 512 + 2 * threadIdx.x;
     const u64 Pq = cprime(primes, K - 1).q;
-    if (!integer)
+    if constexpr (sizeof...(DRA) == 1) {
+        static_assert(LOGP >= 5 && LOGP <= 8, "pass-B chunks of 2^5 .. 2^8 words");
+        constexpr int NSEG = 512 >> LOGP;  // the block's 512 output words of a child: NSEG whole chunks
+        __shared__ __attribute__((aligned(16))) u64 lds[2 * NSEG * bmac_ld(LOGP)];
+        __shared__ __attribute__((aligned(16))) u64 ltw[NSEG * (2 * (1 << LOGP) + 2)];
+        const auto &d = (dra, ...);
+        const HmacDRB db{d.Z + (u64)(slot * CG) * d.zs, d.zs, d.osb, d.osk, d.inv[I], d.inv_q[I],
+                         d.twb + ((u64)kI << logN), d.twbf + ((u64)kI << logN), lds, ltw};
+        if (!integer) hmacm_body<BTF, CG, LOGP>(X1, X0, E, ch, B, l, K, logN, pr, Pq, I, kI, s0, bg * BTF, db);
+        else hmacm_body_int<BTI, CG, LOGP>(X1, X0, E, ch, B, l, K, logN, pr, Pq, I, kI, s0, bg * BTI, db);
+    } else if (!integer)
         hmacm_body<BTF, CG>(X1, X0, E, ch, B, l, K, logN, pr, Pq, I, kI, s0, bg * BTF);
     else if (int_mform)
         hmacm_body_int<BTI, CG>(X1, X0, E, ch, B, l, K, logN, pr, Pq, I, kI, s0, bg * BTI);
@@ -2804,11 +2838,15 @@ __global__ void __launch_bounds__(256, MINW)  // MINW waves per SIMD: 3 -> <= 16
 // The MAC is linear and every term is exact mod q_I, so subtracting them from the canonical MAC gives the same bits as
 // adding them inside it.  Uniform residues almost never have a zero coefficient: a small fixed grid that exits at once
 // when the node has none (zl[0] == 0), else strides over (child, b, I, o).
-template <int CG, int NS>
+// DRA = one HmacDR (after a divide-and-round launch): the children's ACC fields are their outputs
+// OUT = (ACC - NTT(z)) P^-1, and OUT_c[b][k][I][o] -= corr P^-1 (mod q_I): the map ACC -> OUT is linear at a fixed z
+// (z comes from the special-prime limb, corrected before its rounding) and every term is an exact residue, so the
+// words equal those of correcting ACC first.
+template <int CG, int NS, class... DRA>
 __global__ void __launch_bounds__(256)
     k_hmacm_zfix(const HSlots<CG, NS> S, const int *__restrict__ zl, int B, int l, int K, int logN,
                  const DevPrime *__restrict__ primes, const int *__restrict__ Imap, int nI, const u64 *__restrict__ cji,
-                 const u64 *__restrict__ psipow)
+                 const u64 *__restrict__ psipow, const DRA... dra)
 {
     if (zl[0] == 0) return;
     const u64 N = 1ull << logN, N2 = 2 * N;
@@ -2845,18 +2883,31 @@ __global__ void __launch_bounds__(256)
             corr1 = addmod(corr1, mulmod(cc, c.key[(((u64)(J * 2 + 1) * K + kI) << logN) + o], pr), pr.q);
         }
         if ((corr0 | corr1) == 0) continue;
-        u64 *a0 = c.ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + o;
-        u64 *a1 = c.ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + o;
+        u64 *a0, *a1;
+        if constexpr (sizeof...(DRA) == 1) {
+            const auto &d = (dra, ...);
+            corr0 = mulmod(corr0, d.inv[I], pr);
+            corr1 = mulmod(corr1, d.inv[I], pr);
+            a0 = c.ACC + b * d.osb + ((u64)I << logN) + o;
+            a1 = a0 + d.osk;
+        } else {
+            a0 = c.ACC + (((u64)((b * 2 + 0) * (l + 1) + I)) << logN) + o;
+            a1 = c.ACC + (((u64)((b * 2 + 1) * (l + 1) + I)) << logN) + o;
+        }
         *a0 = submod(*a0, corr0, pr.q);
         *a1 = submod(*a1, corr1, pr.q);
     }
 }
 
 // nkids children in slots of CG (the last slot may hold fewer), at most NS slots
-template <int BTF, int BTI, int CG, int NS = 1, int MINW = (BTF * CG <= 8 && BTI * CG <= 8) ? 3 : 2>
+// tsel 0: every target (Imap's level row); 1: P alone; 2 (DRL, with dr): the data targets with the divide-and-round
+// epilogue.  DRL: the launcher carries the epilogue's instantiations (one per chunk size)
+template <int BTF, int BTI, int CG, int NS = 1, bool DRL = false, int MINW = (BTF * CG <= 8 && BTI * CG <= 8) ? 3 : 2>
 static void launch_hmacm(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *zl, const HChildSpec *kids,
-                         int nkids, int B, int l)
+                         int nkids, int B, int l, int tsel = 0, const HmacDR *dr = nullptr)
 {
+    if ((tsel == 2) != (dr != nullptr) || tsel < 0 || tsel > 2 || (tsel == 2 && !(DRL && c.hmac_int)))
+        throw std::logic_error("hoisted MAC: target selection");
     HSlots<CG, NS> S{};
     S.ns = (nkids + CG - 1) / CG;
     if (nkids < 1 || S.ns > NS) throw std::invalid_argument("hoisted MAC: children per launch");
@@ -2865,25 +2916,48 @@ static void launch_hmacm(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int
         ch.c[q % CG] = HChild{kids[q].elt, kids[q].einv, kids[q].key, kids[q].W, kids[q].ACC, kids[q].KW, kids[q].MK};
         ch.n = q % CG + 1;
     }
-    const int nint = c.imap_nint[l], X = (int)(c.N / 512);
-    const int gI = (X * nint + 7) / 8 * 8, gF = (X * (l + 1 - nint) + 7) / 8 * 8;
+    const int *dm = tsel == 0 ? c.imap_at(l) : c.imap_split_at(l) + (tsel == 2 ? 1 : 0);
+    const int nI = tsel == 0 ? l + 1 : tsel == 1 ? 1 : l;
+    const int nint = tsel == 0 ? c.imap_nint[l] : tsel == 1 ? c.imap_pint : c.imap_nint[l] - c.imap_pint;
+    const int X = (int)(c.N / 512);
+    const int gI = (X * nint + 7) / 8 * 8, gF = (X * (nI - nint) + 7) / 8 * 8;
     const int wsplit = gI * ((B + BTI - 1) / BTI), total = wsplit + gF * ((B + BTF - 1) / BTF);
-    k_hmacm<BTF, BTI, CG, MINW, NS><<<dim3((unsigned)(total * S.ns)), 256, 0, c.stream>>>(
-        X1, X0, E, zl, S, B, l, (int)c.K, c.logN, c.primes, c.imap_at(l), l + 1, nint, c.cji, c.psipow, wsplit,
-        c.hmac_int);
+    const dim3 grid((unsigned)(total * S.ns));
+    if constexpr (DRL) {
+        if (tsel == 2) {
+            auto go = [&](auto lp) {
+                constexpr int LOGP = decltype(lp)::value;
+                k_hmacm<BTF, BTI, CG, MINW, NS, LOGP, HmacDR><<<grid, 256, 0, c.stream>>>(
+                    X1, X0, E, zl, S, B, l, (int)c.K, c.logN, c.primes, dm, nI, nint, c.cji, c.psipow, wsplit, 1, *dr);
+            };
+            switch (c.logN / 2) {  // the pass-B chunk of run_modup_fused / divide_round: 2^floor(logN / 2) words
+            case 5: go(std::integral_constant<int, 5>{}); break;
+            case 6: go(std::integral_constant<int, 6>{}); break;
+            case 7: go(std::integral_constant<int, 7>{}); break;
+            case 8: go(std::integral_constant<int, 8>{}); break;
+            default: throw std::invalid_argument("poly_modulus_degree must be 2^10 .. 2^16");
+            }
+            HEC_HIP(hipGetLastError());
+            k_hmacm_zfix<CG, NS, HmacDR><<<256, 256, 0, c.stream>>>(S, zl, B, l, (int)c.K, c.logN, c.primes, dm, nI,
+                                                                    c.cji, c.psipow, *dr);
+            HEC_HIP(hipGetLastError());
+            return;
+        }
+    }
+    k_hmacm<BTF, BTI, CG, MINW, NS><<<grid, 256, 0, c.stream>>>(X1, X0, E, zl, S, B, l, (int)c.K, c.logN, c.primes, dm, nI,
+                                                                nint, c.cji, c.psipow, wsplit, c.hmac_int);
     HEC_HIP(hipGetLastError());
-    k_hmacm_zfix<CG, NS><<<256, 256, 0, c.stream>>>(S, zl, B, l, (int)c.K, c.logN, c.primes, c.imap_at(l), l + 1, c.cji,
-                                                    c.psipow);
+    k_hmacm_zfix<CG, NS><<<256, 256, 0, c.stream>>>(S, zl, B, l, (int)c.K, c.logN, c.primes, dm, nI, c.cji, c.psipow);
     HEC_HIP(hipGetLastError());
 }
 
 int hoisted_group(const Ctx &c) { return c.hmac_cfg == 2 ? HMAC_MAX_CHILDREN : c.hmac_cfg ? 2 : 1; }
 
 void hoisted_mac_group(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *zl, const HChildSpec *kids, int nkids,
-                       int B, int l)
+                       int B, int l, int tsel, const HmacDR *dr)
 {
     static_assert(HMAC_MAX_CHILDREN <= 2 * 3, "3 slots of 2 children");
-    launch_hmacm<4, 2, 2, 3>(c, X1, X0, E, zl, kids, nkids, B, l);
+    launch_hmacm<4, 2, 2, 3, true>(c, X1, X0, E, zl, kids, nkids, B, l, tsel, dr);
 }
 
 void hoisted_mac_multi(Ctx &c, PolyArr X1, PolyArr X0, const u64 *E, const int *zl, const HChildSpec *kids, int nkids,
@@ -3018,6 +3092,120 @@ __device__ __forceinline__ void ntt_round_x(u64 *row, int ts, const TwG &twg, co
         for (int a = 0; a < NQ; ++a) {
             if constexpr (TO_REG) regs[gi * NQ + a] = v[a];
             else row[xb ^ bswz_c<LOGP>(a << (LOGP - S1))] = v[a];
+        }
+    }
+}
+
+// The divide-and-round epilogue of k_hmacm's data targets (hmac_divround).  The Galois permutation maps an aligned
+// 2^m block of NTT positions onto an aligned 2^m block, so the block's accumulators of child q (source positions
+// [s0 & ~511, + 512)) are exactly the aligned 512 output words at ob = kc[q] & ~511: NSEG = 512 / P whole pass-B chunks,
+// the chunks the divide-and-round transform runs.  Per child the chunk twiddles are staged once; per batch entry the
+// two polys' 512 words of Z[b][k][I] (threads 0..127: k = 0, 128..255: k = 1, 4 elements per thread as in k_bmac) go
+// through the forward pass-B rounds in LDS, every thread reads the transformed words of its own output pair from
+// both sets, and stores (acc - NTT(z)) P^-1 with the arithmetic of k_bmac's epilogue.  acc(q, t, i): the reduced sum
+// i of child q, batch entry t (FP64: a double in [-0.53q, 0.53q]; 60-bit: canonical), in source order.
+template <int LOGP, bool FP, int BT, int CG, class AccF>
+__device__ __forceinline__ void hmacm_divround(const HmacDRB &dr, const HChildren<CG> &ch, const u64 *kc,
+                                               const bool *sw, int B, int l, int logN, const DevPrime &pr, int I,
+                                               int b0, const AccF &acc)
+{
+    constexpr int P = 1 << LOGP, NSEG = 512 / P, TPS = P / 4, LD = bmac_ld(LOGP), TWS = 2 * P + 2, SET = NSEG * LD;
+    constexpr bool SWZ = BSwz<LOGP>::on;
+    const int set = (int)threadIdx.x >> 7, tl = (int)threadIdx.x & 127;
+    const int ts = tl % TPS, sg = tl / TPS;
+    u64 *const sbase = dr.lds + set * SET;
+    u64 *const row = sbase + sg * LD;
+    auto addr = [sg](int x) { return sg * LD + x + (x >> 4); };
+    const u64 R = 1ull << (logN - LOGP), two_q = 2 * pr.q;
+    const LdsTw twg{dr.ltw + sg * TWS};
+    auto stage = [&](int li, ulonglong2 w) {  // elements li, li + 1 of the set
+        if constexpr (SWZ) {
+            *(ulonglong2 *)(sbase + (li / P) * LD + bswz<LOGP>(li % P)) = w;
+        } else {
+            sbase[(li / P) * LD + (li % P) + ((li % P) >> 4)] = w.x;
+            sbase[(li / P) * LD + (li % P) + 1 + (((li % P) + 1) >> 4)] = w.y;
+        }
+    };
+    auto rounds = [&] {  // k_bmac's rounds, the last one back into the rows
+        if constexpr (SWZ) {
+            ntt_round_x<LOGP, 0, 2, 4, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 2, 4, 4, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 4, 6, 4, false, FP, false>(row, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_x<LOGP, 6, LOGP, 4, false, FP, false>(row, ts, twg, pr, nullptr);
+        } else {
+            ntt_round_g<LOGP, 0, 2, 4, false, FP, false>(sbase, addr, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_g<LOGP, 2, 4, 4, false, FP, false>(sbase, addr, ts, twg, pr, nullptr);
+            __syncthreads();
+            ntt_round_g<LOGP, 4, LOGP, 4, false, FP, false>(sbase, addr, ts, twg, pr, nullptr);
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < CG; ++q) {
+        if (q >= ch.n) break;  // block-uniform, as every bound below
+        const u32 ob = (u32)kc[q] & ~511u;
+        const int seg0 = (int)(ob >> LOGP), px = (int)((u32)kc[q] & 511u);
+        // the child's chunk twiddles (bmac_body's staging); the previous child's rounds ended at a barrier
+        for (int t = threadIdx.x; t < NSEG * (P - 1); t += 256) {
+            const int sl = t % NSEG, k = t / NSEG;
+            const int st = 31 - __clz(k + 1), i = k + 1 - (1 << st);
+            const u64 gi = R * ((1ull << st) - 1) + (u64)i * R + (u64)(seg0 + sl);
+            if constexpr (FP) dr.ltw[sl * TWS + k] = (u64)__double_as_longlong(dr.twf[gi]);
+            else {
+                const ulonglong2 w = dr.tw[gi];
+                dr.ltw[sl * TWS + 2 * k] = w.x;
+                dr.ltw[sl * TWS + 2 * k + 1] = w.y;
+            }
+        }
+        const u64 *zc = dr.Z + (u64)q * dr.zs + ((u64)I << logN) + ob;
+        u64 *oc = ch.c[q].ACC + ((u64)I << logN) + kc[q];  // a divide-and-round launch: the child's output
+        auto load_z = [&](int b, ulonglong2 &z0, ulonglong2 &z1) {
+            const ulonglong2 *zp = (const ulonglong2 *)(zc + ((u64)((b * 2 + set) * l) << logN));
+            z0 = zp[tl];
+            z1 = zp[tl + 128];
+        };
+        ulonglong2 z0, z1;
+        load_z(b0, z0, z1);
+#pragma unroll
+        for (int t = 0; t < BT; ++t) {
+            const int b = b0 + t;
+            if (b >= B) break;
+            __syncthreads();  // the rows' readers of the previous tile are done
+            stage(2 * tl, z0);
+            stage(2 * (tl + 128), z1);
+            if (t + 1 < BT && b + 1 < B) load_z(b + 1, z0, z1);
+            __syncthreads();
+            rounds();
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const u64 *rb = dr.lds + k * SET + (px >> LOGP) * LD;
+                const int x = px & (P - 1);
+                u64 v0, v1;
+                if constexpr (SWZ) {
+                    const ulonglong2 w = *(const ulonglong2 *)(rb + bswz<LOGP>(x));
+                    v0 = w.x;
+                    v1 = w.y;
+                } else {
+                    v0 = rb[x + (x >> 4)];
+                    v1 = rb[x + 1 + ((x + 1) >> 4)];
+                }
+                const auto a0 = acc(q, t, 2 * k), a1 = acc(q, t, 2 * k + 1);
+                const auto x0 = sw[q] ? a1 : a0, x1 = sw[q] ? a0 : a1;  // the output pair's order
+                u64 r0, r1;
+                if constexpr (FP) {
+                    const double pw = u2d(dr.w);
+                    r0 = fp_canon(fp_mulmod(x0 - __longlong_as_double((long long)v0), pw, pr.qd, pr.qinv), pr.qd, pr.qinv);
+                    r1 = fp_canon(fp_mulmod(x1 - __longlong_as_double((long long)v1), pw, pr.qd, pr.qinv), pr.qd, pr.qinv);
+                } else {
+                    r0 = shoup(x0 + pr.q - csub(csub(v0, two_q), pr.q), dr.w, dr.wq, pr.q);
+                    r1 = shoup(x1 + pr.q - csub(csub(v1, two_q), pr.q), dr.w, dr.wq, pr.q);
+                }
+                st2v(oc + b * dr.osb + k * dr.osk, ulonglong2{r0, r1});
+            }
         }
     }
 }
@@ -3268,7 +3456,7 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
                 }
             }
 #pragma unroll
-            for (int e = 0; e < EPT; e += 2) st2m<2>(dr.out[k] + g0 + e, ulonglong2{r[e], r[e + 1]});
+            for (int e = 0; e < EPT; e += 2) st2v(dr.out[k] + g0 + e, ulonglong2{r[e], r[e + 1]});
             if (k == 0) __syncthreads();  // the rows are staged again
         };
         load_z(0);

@@ -76,7 +76,10 @@ int hec_context_synchronize(hec_context *ctx);
  * targets on the round-5 loop), "nt_e" (0: the hoisted digits stored with the default cache policy instead of
  * non-temporally), "mac_divround" (1: the per-rotation key switch accumulates the special-prime target first and the
  * data targets' fused MAC kernel divides-and-rounds its own accumulators; 0: the separate divide-and-round pass B;
- * HEC_MAC_DIVROUND at context creation, HEC_EINVAL when out of range), "kernel_memops" (0: workspace fills and
+ * HEC_MAC_DIVROUND at context creation, HEC_EINVAL when out of range), "hmac_divround" (1: the same order for the
+ * children of a hoisted node, a sibling group at a time: the hoisted MAC kernel's data targets divide-and-round their
+ * accumulators into the children's rotation buffers; 0: the separate pass B; HEC_HMAC_DIVROUND at context creation,
+ * HEC_EINVAL when out of range; applies with "hmac" 2, "hmac_int" 1 and "fan" 1), "kernel_memops" (0: workspace fills and
  * device copies through the runtime's hipMemsetAsync / hipMemcpyAsync instead of engine kernels; A/B only,
  * DESIGN.md §4.8), "prng_group" (0..16: PRNG buffers per wavefront of the key generator's BLAKE2Xb kernel, 0 = chosen per
  * launch; every value draws the same words), and three debug switches:
@@ -86,7 +89,7 @@ int hec_context_synchronize(hec_context *ctx);
  * bit-identical.  Applies to the context and its batch lanes; HEC_EINVAL for an unknown name, and for a value
  * outside an enumerated knob's range ("split_bfly" 0..4, "hmac" 0..2, "hmac_odd3" 0..1, "hoist_scan" 0..1,
  * "nttb_shfl" 0..2, "nttb_shfl_dr" 0..1, "moddown1" 0..1, "hmac_int" 0..1, "nt_e" 0..1,
- * "mac_divround" 0..1, "prng_group" 0..16, "rot_add" 0..1).  "math_chunk" (0..65535) caps the ciphertexts per pass
+ * "mac_divround" 0..1, "hmac_divround" 0..1, "prng_group" 0..16, "rot_add" 0..1).  "math_chunk" (0..65535) caps the ciphertexts per pass
  * of the he::math calls and of hec_multiply_relin_rescale_many / hec_sum_elems_many below; 0 is automatic, a negative
  * value HEC_EINVAL.  "rot_add": 1 the rotate-and-accumulate steps of hec_sum_elems_many add the accumulator in the
  * key switch's last stage (k_bmac's divide-and-round epilogue, k_moddown1), 0 in a k_ew_add launch after it. */
