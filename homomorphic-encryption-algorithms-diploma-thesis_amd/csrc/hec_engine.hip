@@ -6,6 +6,12 @@
 // routines take B ciphertexts in one strided array so that one launch sequence (and one read of
 // the key) serves the whole batch; the single-object C-ABI calls are the B = 1 case.
 //
+// This file holds the objects' lifecycle, context setup and options, the key switch, the rotation trie and the matvec,
+// the evaluator calls, encode, decode, keygen and the wire-format glue, the sharded calls, the primitives and the
+// profile calls.  The library-level layers over many ciphertexts (he::fft, he::math, he::linalg's element-wise
+// products and slot sums) live in hec_batched.hip, written over the building blocks that hec_host.h declares; the
+// object structs, the error guard, Scratch and ProfScope are in hec_host.h as well.
+//
 // Key switch dataflow (SEAL 4.1 Evaluator::switch_key_inplace, per-prime digits + special prime P,
 // SURVEY §8(a) a5), B targets T[b] (NTT form, l limbs):
 //   (1) D[b][J]    = INTT_J(T[b][J])                                    ntt_strided (inverse)
@@ -23,11 +29,12 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <thread>
 #include <tuple>
 
-#include "hec_internal.h"
+#include "hec_host.h"
 #include "hec_keygen_host.h"
 #include "hec_live.h"
 
@@ -35,118 +42,13 @@
 #include <dlfcn.h>
 #include <unistd.h>
 #include <rccl/rccl.h>
-#include "hecdna.h"
 
 using namespace hec;
 using u128 = unsigned __int128;
 
-// =============================================================================== objects ===
-// The communicator of the sharded matvec (one process per GPU): RCCL over xGMI (hec_comm_init) or a caller's host
-// collectives (hec_comm_init_ops).  shard_agree needs only allreduce_f64; the data exchange sums the ranks' partial
-// accumulators in u64.
-struct HecComm {
-    virtual ~HecComm() = default;
-    // in place over the world, host memory: op HEC_REDUCE_MIN / HEC_REDUCE_MAX
-    virtual void allreduce_f64(double *host, std::size_t n, int op, hipStream_t s) = 0;
-    // in place over the world, a device buffer ordered on stream s: the sum (exact: world <= 8, residues < 2^60)
-    virtual void allreduce_u64_sum(u64 *dev, std::size_t n, hipStream_t s) = 0;
-};
-struct hec_context {
-    Ctx c;
-    // batch lanes (matvec_lanes): contexts sharing this one's device tables, each with its own HIP
-    // stream, workspace and zero flag, built on first use
-    std::vector<hec_context *> lanes;
-    // persistent events of matvec_lanes (created with the first lane, destroyed with the context): the lanes
-    // wait on lanes_start, the context stream waits on each lane's lane_done.  An event destroyed right after
-    // a hipStreamWaitEvent on it could let that wait pass early (a rare whole-lane race seen at full size).
-    hipEvent_t lanes_start = nullptr, lane_done = nullptr;
-    // multi-GPU (hec_comm_init): this process's rank in a world of one process per GPU, RCCL communicator
-    int rank = 0, world = 1;
-    HecComm *comm = nullptr;
-    u64 gen = 0;  // this context's entry in the live-context registry (hec_live.h)
-};
-// Every device object records its context by address and generation (hec_live.h) and its device, so that its destroy
-// can free its memory after the context is gone.  bind() is the only place that sets these.
-struct DevObject {
-    hec_context *ctx = nullptr;
-    u64 ctx_gen = 0;
-    int device = 0;
-};
-struct hec_ciphertext : DevObject {
-    u64 *d = nullptr;
-    std::size_t cap = 0;  // words
-    std::size_t size = 0, level = 0;
-    double scale = 1.0;
-};
-struct hec_plaintext : DevObject {
-    u64 *d = nullptr;
-    std::size_t cap = 0;
-    std::size_t level = 0;
-    double scale = 1.0;
-};
-struct hec_kswitch_key : DevObject {
-    u64 *d = nullptr;
-};
-struct hec_secret_key : DevObject {  // seal::SecretKey: u64[K][N], NTT form, key level
-    u64 *d = nullptr;
-    std::size_t words = 0;
-};
-struct hec_public_key : DevObject {  // seal::PublicKey: u64[2][K][N], NTT form, key level
-    u64 *d = nullptr;
-};
-struct hec_galois_keys : DevObject {
-    std::map<u32, u64 *> keys;
-    std::map<u32, u64 *> negw;  // hoisted mod-up: W_elt[I] = NTT_I(sign mask of elt), built on first use
-    // hoisted MAC: KW[elt, l][k][I] = sum_{J<l, J!=I} (q_J mod q_I) key_elt[J][k][I] mod q_I, built on first
-    // use per level, dropped when the key is replaced
-    std::map<std::pair<u32, int>, u64 *> kw;
-    std::map<u32, u64 *> mkey;  // hoisted MAC: the key in MAC form and source order (mac_key_table), first use
-    void drop_kw(u32 elt)  // the tables derived from the key's words (KW at every level, MK)
-    {
-        if (auto m = mkey.find(elt); m != mkey.end()) {
-            (void)hipFree(m->second);
-            mkey.erase(m);
-        }
-        for (auto it = kw.begin(); it != kw.end();) {
-            if (it->first.first == elt) {
-                (void)hipFree(it->second);
-                it = kw.erase(it);
-            } else {
-                ++it;
-            }
-        }
-    }
-};
+thread_local std::string hec::g_err;
 
 namespace {
-
-thread_local std::string g_err;
-
-template <class F>
-int guard(F &&f)
-{
-    try {
-        f();
-        return HEC_OK;
-    } catch (const HipError &e) {
-        g_err = e.what();
-        return HEC_EDEVICE;
-    } catch (const std::invalid_argument &e) {
-        g_err = e.what();
-        return HEC_EINVAL;
-    } catch (const std::logic_error &e) {
-        g_err = e.what();
-        return HEC_ELOGIC;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        return HEC_EDEVICE;
-    }
-}
-
-void need(bool cond, const char *msg)
-{
-    if (!cond) throw std::invalid_argument(msg);
-}
 
 // ------------------------------------------------------------------ host number theory -----
 u64 powm(u64 b, u64 e, u64 q)
@@ -193,12 +95,18 @@ bool isprime(u64 n)
     return true;
 }
 u64 shoupq(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
+}  // namespace
+// Here and below, a `namespace hec` block holds a building block that hec_host.h declares for hec_batched.hip; the rest
+// of this file's helpers stay in the anonymous namespace.
+namespace hec {
 u32 brev(u32 x, int bits)
 {
     u32 r = 0;
     for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1 - i);
     return r;
 }
+}  // namespace hec
+namespace {
 // SEAL util::try_minimal_primitive_root: the smallest primitive 2N-th root of unity mod q
 u64 minimal_root(u64 two_n, u64 q)
 {
@@ -216,6 +124,8 @@ u64 minimal_root(u64 two_n, u64 q)
     }
     return best;
 }
+}  // namespace
+namespace hec {
 bool are_close(double a, double b)  // SEAL util::are_close
 {
     const double sf = std::max({std::fabs(a), std::fabs(b), 1.0});
@@ -225,6 +135,8 @@ bool scale_ok(const Ctx &c, double scale, std::size_t level)  // SEAL is_scale_w
 {
     return !(scale <= 0 || (int)std::log2(scale) >= c.total_bits(level));
 }
+}  // namespace hec
+namespace {
 std::vector<int> naf(int value)  // SEAL util::naf: least-significant term first
 {
     std::vector<int> res;
@@ -237,6 +149,8 @@ std::vector<int> naf(int value)  // SEAL util::naf: least-significant term first
     }
     return res;
 }
+}  // namespace
+namespace hec {
 u32 elt_from_step(const Ctx &c, int step)  // SEAL GaloisTool::get_elt_from_step
 {
     const u32 n = (u32)c.N, m = 2 * n;
@@ -261,6 +175,8 @@ void rotation_elts(const Ctx &c, int steps, const hec_galois_keys &gk, std::vect
     for (int s : terms)
         if ((std::size_t)std::abs(s) != (c.N >> 1)) rotation_elts(c, s, gk, out);
 }
+}  // namespace hec
+namespace {
 
 // ------------------------------------------------------------------ device memory ----------
 u64 *dalloc(std::size_t words)
@@ -271,90 +187,8 @@ u64 *dalloc(std::size_t words)
     return (u64 *)p;
 }
 
-// stack-style carving of the context workspace; kernels are stream ordered, so a region released
-// here may be reused by the next enqueued operation.
-struct Scratch {
-    Ctx &c;
-    std::size_t top = 0;
-    explicit Scratch(Ctx &cc, std::size_t words) : c(cc)
-    {
-        c.ws.reserve(words, c.stream);
-        ++c.ws.depth;
-    }
-    ~Scratch()
-    {
-        if (--c.ws.depth == 0 && !c.ws.defer_free && !c.ws.retired.empty()) {
-            try {
-                c.ws.reclaim(c.stream);
-            } catch (...) {  // keep them for release(); a destructor must not throw
-            }
-        }
-    }
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    u64 *take(std::size_t w)
-    {
-        w = (w + 63) & ~(std::size_t)63;
-        if (top + w > c.ws.words) throw std::logic_error("workspace overflow");
-        u64 *p = c.ws.base + top;
-        top += w;
-        if (c.poison) dev_fill(c, p, 0xFFFFFFFFu, w * sizeof(u64));
-        return p;
-    }
-};
-
 // ------------------------------------------------------------------ profiling -------------
-// Per-class GPU time of the engine's phases.  prof_mode 1: event pair + synchronize per scope;
-// prof_mode 2: event pairs from a reusable pool recorded asynchronously (no host sync inside the
-// call), resolved when the profile is read.
-struct ProfScope {
-    Ctx &c;
-    const char *name;
-    double bytes = 0;
-    int kl = 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipEvent_t pool_event()
-    {
-        if (c.ev_used == c.ev_pool.size()) {
-            hipEvent_t e;
-            HEC_HIP(hipEventCreate(&e));
-            c.ev_pool.push_back(e);
-        }
-        return c.ev_pool[c.ev_used++];
-    }
-    ProfScope(Ctx &cc, const char *n, double limbs = 0, int launches = 1)
-        : c(cc), name(n), bytes(limbs * 8.0 * (double)cc.N), kl(launches)
-    {
-        if (!c.prof_mode) return;
-        if (c.prof_mode == 2) {
-            e0 = pool_event();
-            e1 = pool_event();
-        } else {
-            HEC_HIP(hipEventCreate(&e0));
-            HEC_HIP(hipEventCreate(&e1));
-        }
-        HEC_HIP(hipEventRecord(e0, c.stream));
-    }
-    ~ProfScope()
-    {
-        if (!c.prof_mode || !e0) return;
-        (void)hipEventRecord(e1, c.stream);
-        if (c.prof_mode == 2) {
-            c.prof_pend.push_back({name, e0, e1, bytes, kl});
-            return;
-        }
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        auto &r = c.prof_tab[name];
-        r.ms += ms;
-        r.n += 1;
-        r.bytes += bytes;
-        r.kl += kl;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-};
+// the pending event pairs of ProfScope (hec_host.h) under prof_mode 2, resolved when the profile is read
 void prof_resolve(Ctx &c)
 {
     if (c.prof_pend.empty()) return;
@@ -373,10 +207,14 @@ void prof_resolve(Ctx &c)
 }
 
 // ------------------------------------------------------------------ batched building blocks
+}  // namespace
+namespace hec {
 std::size_t ks_words(const Ctx &c, std::size_t B, std::size_t l)
 {
     return c.N * B * (l + (l + 1) * l + 2 * (l + 1) + 2 * l) + 4 * 64;
 }
+}  // namespace hec
+namespace {
 
 // the separate add of a key switch's optional addend: OUT += ADD (both polys), where the last stage did not add it
 static void add_after(Ctx &c, PolyArr OUT, PolyArr ADD, int B, int l)
@@ -685,13 +523,15 @@ const u64 *galois_mkey(hec_context *ctx, hec_galois_keys &gk, u32 elt)
     return MK;
 }
 
+}  // namespace
+namespace hec {
 // X (size 2) -> OUT = apply_galois(X, elt) followed by key switching (SEAL apply_galois_inplace).
 // When OUT does not alias X the permutation is applied inside the key switch's loads (the INTT of c1,
 // the target reuse in the MAC, the c0 add in the mod-down) and never materialised; otherwise X is
 // first permuted into scratch.
 // ADD (optional): OUT = that + ADD (keyswitch's second addend; ADD may be OUT, and may be X when OUT is not)
 void galois_ks(Ctx &c, Scratch &s, PolyArr X, PolyArr OUT, int B, int l, u32 elt, const u64 *key,
-               PolyArr ADD = PolyArr{})
+               PolyArr ADD)
 {
     const u64 N = c.N;
     const bool alias = OUT.p == X.p || !c.fuse_galois;
@@ -708,6 +548,8 @@ void galois_ks(Ctx &c, Scratch &s, PolyArr X, PolyArr OUT, int B, int l, u32 elt
     keyswitch(c, s, PolyArr{S + (u64)B * l * N, l * N, 0}, key, PolyArr{S, l * N, 0}, 1, OUT, B, l, 1, ADD);
     s.top = top;
 }
+}  // namespace hec
+namespace {
 
 // divide-and-round by q_{l-1}: X = B entries of nk polys at level l -> OUT at level l-1
 void rescale_batch(Ctx &c, Scratch &s, PolyArr X, int B, int nk, int l, PolyArr OUT)
@@ -723,9 +565,26 @@ void rescale_batch(Ctx &c, Scratch &s, PolyArr X, int B, int nk, int l, PolyArr 
                  c.ql_inv_q[l].data(), Z);
     s.top = top;
 }
+}  // namespace
+namespace hec {
 std::size_t rescale_words(const Ctx &c, std::size_t B, std::size_t nk, std::size_t l)
 {
     return c.N * B * nk * (1 + 2 * l) + 3 * 64;
+}
+
+// The tail of every ct x ct product (relinearize, rescale_to_next): the B size-3 entries A3 ([B][3][l][N]) are
+// relinearized in place, then their first two polys divided-and-rounded into OUT at level l - 1.  relin_scope names a
+// profile class around the key switch alone; ProfScope keeps the pointer, so it is a string literal
+void relin_rescale(Ctx &c, Scratch &s, u64 *A3, const u64 *rk, int B, int l, PolyArr OUT, const char *relin_scope)
+{
+    const u64 N = c.N, S3 = 3 * (u64)l * N;
+    const PolyArr Aa{A3, S3, (u64)l * N};
+    {
+        std::optional<ProfScope> pr;
+        if (relin_scope) pr.emplace(c, relin_scope);
+        keyswitch(c, s, PolyArr{A3 + 2 * (u64)l * N, S3, 0}, rk, Aa, 2, Aa, B, l);
+    }
+    rescale_batch(c, s, Aa, B, 2, l, OUT);
 }
 
 void set_device(hec_context *ctx)
@@ -740,16 +599,10 @@ void d2d(Ctx &c, void *dst, const void *src, std::size_t words)
     if (c.kernel_memops) dev_copy64(c, (u64 *)dst, (const u64 *)src, words);
     else HEC_HIP(hipMemcpyAsync(dst, src, words * sizeof(u64), hipMemcpyDeviceToDevice, c.stream));
 }
+}  // namespace hec
+namespace {
 
 // ------------------------------------------------------------------ device objects ---------
-// SEAL's is_valid_for messages, one per object kind
-constexpr const char *BAD_CT = "encrypted is not valid for encryption parameters";
-constexpr const char *BAD_PLAIN = "plain is not valid for encryption parameters";
-constexpr const char *BAD_SK = "secret key is not valid for encryption parameters";
-constexpr const char *BAD_PK = "public key is not valid for encryption parameters";
-constexpr const char *BAD_RK = "relin_keys is not valid for encryption parameters";
-constexpr const char *BAD_GK = "galois_keys is not valid for encryption parameters";
-
 void bind(DevObject &o, hec_context *ctx)
 {
     o.ctx = ctx;
@@ -767,7 +620,8 @@ auto make(hec_context *ctx)
     bind(*o, ctx);
     return o;
 }
-
+}  // namespace
+namespace hec {
 // Calls that take a context: the object must belong to this very context (a later context at the same address has
 // another generation).
 void check_obj(const hec_context *ctx, const DevObject *o, const char *msg)
@@ -779,6 +633,8 @@ void check_ct(const hec_context *ctx, const hec_ciphertext *a)
     check_obj(ctx, a, BAD_CT);
     need(a->level >= 1 && a->level <= ctx->c.L && a->size >= 2 && a->d, BAD_CT);
 }
+}  // namespace hec
+namespace {
 void check_plain_data(const hec_context *ctx, const hec_plaintext *p)  // holds data; the caller compares the level
 {
     check_obj(ctx, p, BAD_PLAIN);
@@ -824,6 +680,21 @@ void grow(T *o, std::size_t words, std::size_t keep_words = 0)
     o->cap = words;
     if (c.poison) dev_fill(c, o->d + keep_words, 0xFFFFFFFFu, (words - keep_words) * sizeof(u64));
 }
+
+}  // namespace
+namespace hec {
+// The one output store: o becomes `size` polys of `level` limbs copied from src.  grow() comes before the copy (it may
+// drain the stream and free the old buffer).  A call whose outputs may be its inputs reads what it needs of the inputs'
+// host fields before its first store, and enqueues its gathers before it
+void store_ct(Ctx &c, hec_ciphertext *o, const u64 *src, std::size_t size, std::size_t level, double scale)
+{
+    const std::size_t w = size * level * c.N;
+    grow(o, w);
+    d2d(c, o->d, src, w);
+    o->size = size; o->level = level; o->scale = scale;
+}
+}  // namespace hec
+namespace {
 
 // The device memory an object owns
 template <class T>
@@ -1233,28 +1104,19 @@ void matvec_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec
             return;
         }
     }
-    const u64 accw = pt ? S2 : S3;  // accumulator words per output
-    if (!finish) {
-        for (std::size_t i = 0; i < p; ++i) {
-            grow(out[i], accw);
-            d2d(c, out[i]->d, ACC3 + i * S3, accw);
-            out[i]->size = pt ? 2 : 3; out[i]->level = l; out[i]->scale = ps[i];
-        }
+    if (!finish) {  // the accumulators as they are: size 3 for ct x ct, size 2 for ct x pt
+        for (std::size_t i = 0; i < p; ++i) store_ct(c, out[i], ACC3 + i * S3, pt ? 2 : 3, l, ps[i]);
         return;
     }
-    if (!pt) {  // relinearize (SMART_RELIN == 1: once per output) — he_linalg.cpp:1000
-        ProfScope pr(c, "relin");
-        keyswitch(c, s, PolyArr{ACC3 + 2 * l * N, S3, 0}, rk->d, Aa, 2, Aa, (int)p, (int)l);
-    }
-    const u64 So = 2 * (l - 1) * N;  // rescale (he_linalg.cpp:1001)
+    const u64 So = 2 * (l - 1) * N;
     u64 *O = s.take(p * So);
-    rescale_batch(c, s, Aa, (int)p, 2, (int)l, PolyArr{O, So, (l - 1) * N});
+    const PolyArr Oa{O, So, (l - 1) * N};
+    // relinearize (SMART_RELIN == 1: once per output, he_linalg.cpp:1000) and rescale (:1001); ct x pt products are
+    // size 2 and only rescale
+    if (pt) rescale_batch(c, s, Aa, (int)p, 2, (int)l, Oa);
+    else relin_rescale(c, s, ACC3, rk->d, (int)p, (int)l, Oa, "relin");
     const double ql = (double)c.q[l - 1];
-    for (std::size_t i = 0; i < p; ++i) {
-        grow(out[i], So);
-        d2d(c, out[i]->d, O + i * So, So);
-        out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = ps[i] / ql;
-    }
+    for (std::size_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, ps[i] / ql);
 }
 
 
@@ -2062,10 +1924,7 @@ int hec_ciphertext_copy(hec_ciphertext *dst, const hec_ciphertext *src)
         need(dst && src && dst->ctx == src->ctx && dst->ctx_gen == src->ctx_gen, "null argument");
         Ctx &c = live(dst, BAD_CT);
         if (dst == src) return;
-        const std::size_t w = src->size * src->level * c.N;
-        grow(dst, w);
-        d2d(c, dst->d, src->d, w);
-        dst->size = src->size; dst->level = src->level; dst->scale = src->scale;
+        store_ct(c, dst, src->d, src->size, src->level, src->scale);
     });
 }
 int hec_ciphertext_export_device(const hec_ciphertext *ct, void *dev_dst)
@@ -2189,6 +2048,9 @@ static std::complex<double> get(u64 m, const std::vector<std::complex<double>> &
     return {a.real(), -a.imag()};
 }
 };
+}  // namespace
+extern "C++" {  // C++ linkage inside the C-ABI block, as hec_host.h declares it
+namespace hec {
 void encoder_tables(Ctx &c)
 {
     if (c.enc_map) return;
@@ -2223,7 +2085,8 @@ void encoder_tables(Ctx &c)
     c.enc_map = dm;
     c.enc_tw = dt;
 }
-}  // namespace
+}  // namespace hec
+}  // extern "C++"
 
 int hec_encode(hec_context *ctx, const double *re, const double *im, uint64_t n_values, uint64_t count, double scale,
                uint64_t level, hec_plaintext *const *out)
@@ -2297,30 +2160,15 @@ static u64 exact_residue(double a, u64 q)
     return r;
 }
 
-// The data primes of a modulus chain on the host: what the scalar encoder and the scale checks need, with or without a
-// device context (hec_math_plan has none)
-struct Chain {
-    const u64 *q = nullptr;
-    std::size_t L = 0;
-    int total_bits(std::size_t level) const
-    {
-        int b = 0;
-        for (std::size_t i = 0; i < level; ++i) b += 64 - __builtin_clzll(q[i]);
-        return b;
-    }
-    bool scale_ok(double scale, std::size_t level) const  // SEAL is_scale_within_bounds
-    {
-        return !(scale <= 0 || (int)std::log2(scale) >= total_bits(level));
-    }
-};
+extern "C++" {  // as encoder_tables above
+namespace hec {
 // SEAL 4.1 CKKSEncoder::encode_internal(double value, parms_id, scale, destination) up to its fill: the checks, in its
-// order, and the word of every limb
-static void scalar_words_chain(const Chain &c, double value, double scale, std::size_t level, u64 *words);
-static void scalar_words(const Ctx &c, double value, double scale, std::size_t level, u64 *words)
+// order, and the word of every limb (Chain: hec_host.h)
+void scalar_words(const Ctx &c, double value, double scale, std::size_t level, u64 *words)
 {
     scalar_words_chain(Chain{c.q.data(), c.L}, value, scale, level, words);
 }
-static void scalar_words_chain(const Chain &c, double value, double scale, std::size_t level, u64 *words)
+void scalar_words_chain(const Chain &c, double value, double scale, std::size_t level, u64 *words)
 {
     if (level < 1 || level > c.L) throw std::invalid_argument("parms_id is not valid for encryption parameters");
     const int total = c.total_bits(level);
@@ -2339,6 +2187,8 @@ static void scalar_words_chain(const Chain &c, double value, double scale, std::
         words[j] = neg && r ? q - r : r;  // negate_uint_mod
     }
 }
+}  // namespace hec
+}  // extern "C++"
 
 int hec_encode_scalar(hec_context *ctx, double value, double scale, uint64_t level, hec_plaintext *out)
 {
@@ -3585,893 +3435,10 @@ int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, 
         Scratch s(c, p * (S3 + So) + ks_words(c, p, l) + rescale_words(c, p, 2, l) + 256);
         u64 *A3 = s.take(p * S3), *O = s.take(p * So);
         for (uint64_t i = 0; i < p; ++i) d2d(c, A3 + i * S3, acc[i]->d, S3);
-        const PolyArr Aa{A3, S3, l * N};
-        keyswitch(c, s, PolyArr{A3 + 2 * l * N, S3, 0}, rk->d, Aa, 2, Aa, (int)p, (int)l);
-        rescale_batch(c, s, Aa, (int)p, 2, (int)l, PolyArr{O, So, (l - 1) * N});
-        std::vector<double> sc(p);
+        relin_rescale(c, s, A3, rk->d, (int)p, (int)l, PolyArr{O, So, (l - 1) * N});
+        std::vector<double> sc(p);  // out[i] may be an acc[j]: every scale is read before the first store
         for (uint64_t i = 0; i < p; ++i) sc[i] = acc[i]->scale / (double)c.q[l - 1];
-        for (uint64_t i = 0; i < p; ++i) {
-            grow(out[i], So);
-            d2d(c, out[i]->d, O + i * So, So);
-            out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = sc[i];
-        }
-    });
-}
-
-// ------------------------------------------------------------------ he::fft ----------------
-// Both transforms walk a chain of multiply_plain + rescale stages (reference src/core/he_fft.cpp).  A stage runs over
-// all of its ciphertexts in a fixed number of launches: the stage's plaintexts from the batched encoder, the
-// last-limb products, their batched INTT, the rounding limbs (divide_round's pass A) and the fused
-// multiply-rescale-sum pass (hec_kernels.hip FftIOB); the in-slot FFT adds its two batched rotations.  The twiddles
-// and diagonals come from hec_fft_host.cpp alone.  Outputs are written after the last stage, so an error leaves them
-// untouched.
-namespace {
-constexpr int FFT_MAX_JOBS = 65535;  // blocks along y of one NTT pass
-
-struct FftPlan {
-    std::size_t n = 0, B = 0, l0 = 0;
-    int stages = 0, total = 0;  // total = stages + the inverse's 1/n step
-    double scale = 0;
-    std::vector<double> sc;     // the scale entering step s; sc[total] the result's
-    // the checks shared by hec_fft and hec_bfft: `count` ciphertexts, n the transform size (a class member: no C
-    // language linkage inside the C-ABI block)
-    static FftPlan make(hec_context *ctx, const hec_ciphertext *const *in, uint64_t count, uint64_t n, int inverse,
-                        hec_ciphertext *const *out);
-};
-
-FftPlan FftPlan::make(hec_context *ctx, const hec_ciphertext *const *in, uint64_t count, uint64_t n, int inverse,
-                      hec_ciphertext *const *out)
-{
-    need(ctx && in && out && count >= 1, "null argument");
-    const Ctx &c = ctx->c;
-    need(n >= 1 && !(n & (n - 1)), "n must be a power of two");
-    for (uint64_t i = 0; i < count; ++i) {
-        check_ct(ctx, in[i]);
-        check_obj(ctx, out[i], BAD_CT);
-        need(in[i]->size == 2, "encrypted size must be 2");
-        need(in[i]->level == in[0]->level, "encrypted1 and encrypted2 parameter mismatch");
-        need(std::memcmp(&in[i]->scale, &in[0]->scale, sizeof(double)) == 0, "scale mismatch");
-    }
-    FftPlan p;
-    p.n = n;
-    p.l0 = in[0]->level;
-    while ((std::size_t(1) << p.stages) < n) ++p.stages;
-    p.total = p.stages + (inverse ? 1 : 0);
-    if (p.total > 0 && p.l0 < (std::size_t)p.total + 1)
-        throw std::invalid_argument("end of modulus switching chain reached");
-    // every step encodes at the operands' scale and level, multiplies (the scale squares) and rescales
-    double sc = in[0]->scale;
-    p.sc.push_back(sc);
-    for (int s = 0; s < p.total; ++s) {
-        const std::size_t l = p.l0 - s;
-        need(scale_ok(c, sc, l), "scale out of bounds");
-        need(scale_ok(c, sc * sc, l), "scale out of bounds");
-        sc = sc * sc / (double)c.q[l - 1];
-        p.sc.push_back(sc);
-    }
-    return p;
-}
-
-// the encoder's "encoded values are too large" check over the maxima of `count` encoded vectors at `level`
-void fft_check_maxabs(const Ctx &c, const u64 *mx, std::size_t count, std::size_t level)
-{
-    for (std::size_t v = 0; v < count; ++v) {
-        double maxabs;
-        std::memcpy(&maxabs, &mx[v], sizeof(double));
-        if (!std::isfinite(maxabs)) throw std::invalid_argument("encoded values are too large");
-        const int max_bits = (int)std::ceil(std::log2(std::max(maxabs, 1.0))) + 1;
-        if (max_bits >= c.total_bits(level)) throw std::invalid_argument("encoded values are too large");
-    }
-}
-
-// one multiply-rescale-sum stage over source entries W (nsrc entries of 2 polys at level l) -> OUT (nout entries at
-// level l - 1); P = the stage's plaintexts [..][l][N]; half / nb / nt as FftIOB
-void fft_stage_core(Ctx &c, const u64 *W, const u64 *P, u64 *Y, u64 *Z, u64 *OUT, int nsrc, int nout, int l, int half,
-                    int nb, int nt, int npt)
-{
-    const u64 N = c.N, sb = 2 * (u64)l * N, sk = (u64)l * N;
-    {
-        ProfScope k(c, "k:k_fft_lastprod/fft", 4.0 * nsrc + npt);
-        fft_lastprod(c, W, sb, sk, P, sk, Y, nsrc, 2, l, half, nb);
-    }
-    {
-        ProfScope k(c, "k:k_ntt/fft_intt", 8.0 * nsrc, 2);
-        const int pm[1] = {l - 1};
-        ntt_strided(c, true, Y, N, Y, N, 1, pm, 2 * nsrc);
-    }
-    {
-        ProfScope k(c, "k:k_ntt/fft_round_a", 2.0 * nsrc * l);
-        fft_round_limbs(c, Y, Z, nsrc, 2, l);
-    }
-    {  // Z and the source data limbs read once each, the plaintexts' data limbs, the outputs
-        ProfScope k(c, "k:k_ntt/fft_mrs", (4.0 * nsrc + 2.0 * nout + npt) * (l - 1));
-        fft_mrs(c, Z, W, sb, sk, P, sk, PolyArr{OUT, 2 * (u64)(l - 1) * N, (u64)(l - 1) * N}, nout, 2, l, half, nb, nt);
-    }
-}
-
-// the inverse's last step: every entry times the scalar plaintext of 1 / n, rescaled
-void fft_scale_step(Ctx &c, const u64 *W, u64 *P, u64 *Y, u64 *Z, u64 *OUT, int cnt, int l, double n, double scale)
-{
-    u64 words[HEC_MAXL + 1];
-    scalar_words(c, 1.0 / n, scale, (std::size_t)l, words);
-    fill_limbs(c, P, l, words);
-    fft_stage_core(c, W, P, Y, Z, OUT, cnt, cnt, l, 0, cnt, 1, 1);
-}
-
-void fft_store(Ctx &c, const u64 *W, hec_ciphertext *const *out, std::size_t cnt, std::size_t l, double scale)
-{
-    const std::size_t So = 2 * l * c.N;
-    for (std::size_t i = 0; i < cnt; ++i) {
-        grow(out[i], So);
-        d2d(c, out[i]->d, W + i * So, So);
-        out[i]->size = 2;
-        out[i]->level = l;
-        out[i]->scale = scale;
-    }
-}
-}  // namespace
-
-int hec_fft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t n, int inverse, hec_ciphertext *const *out)
-{
-    return guard([&] {
-        set_device(ctx);
-        const FftPlan p = FftPlan::make(ctx, in, n, n, inverse, out);
-        Ctx &c = ctx->c;
-        const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
-        if (p.total == 0) {  // n = 1 forward: copies
-            if (out[0] != in[0]) {
-                grow(out[0], S0);
-                d2d(c, out[0]->d, in[0]->d, S0);
-                out[0]->size = 2; out[0]->level = l0; out[0]->scale = in[0]->scale;
-            }
-            return;
-        }
-        need(n * 2 * (l0 - 1) <= (uint64_t)FFT_MAX_JOBS, "too many ciphertexts for one stage");
-        // twiddles of every stage, uploaded once: stage m holds 1 (the identity plaintext) and w_m^k, k < m / 2
-        std::vector<double> tre, tim;
-        for (std::size_t m = 2; m <= n; m <<= 1) {
-            const std::size_t o = tre.size();
-            tre.resize(o + 1 + m / 2);
-            tim.resize(o + 1 + m / 2);
-            tre[o] = 1.0;
-            tim[o] = 0.0;
-            need(hec_fft_twiddles(m, inverse, &tre[o + 1], &tim[o + 1]) == HEC_OK, "n must be a power of two");
-        }
-        const std::size_t ntw = tre.size(), npmax = n / 2 + 1;
-        encoder_tables(c);
-        Scratch s(c, 2 * n * S0 + npmax * l0 * N + 2 * n * N + 2 * n * (l0 - 1) * N + npmax * 2 * N + 3 * ntw +
-                         16 * 64);
-        u64 *Wa = s.take(n * S0), *Wb = s.take(n * S0), *P = s.take(npmax * l0 * N), *Y = s.take(2 * n * N);
-        u64 *Z = s.take(std::max<std::size_t>(2 * n * (l0 - 1) * N, 1));
-        double *work = reinterpret_cast<double *>(s.take(npmax * 2 * N));
-        double *dre = reinterpret_cast<double *>(s.take(ntw)), *dim = reinterpret_cast<double *>(s.take(ntw));
-        u64 *dmx = s.take(ntw);
-        if (ntw) {
-            HEC_HIP(hipMemcpyAsync(dre, tre.data(), ntw * sizeof(double), hipMemcpyHostToDevice, c.stream));
-            HEC_HIP(hipMemcpyAsync(dim, tim.data(), ntw * sizeof(double), hipMemcpyHostToDevice, c.stream));
-        }
-        int lg = 0;
-        while ((std::size_t(1) << lg) < n) ++lg;
-        for (std::size_t j = 0; j < n; ++j)  // the working array: the input in bit-reversed order
-            d2d(c, Wa + j * S0, in[lg ? brev((u32)j, lg) : 0]->d, S0);
-        std::size_t l = l0, off = 0;
-        int step = 0;
-        for (std::size_t m = 2; m <= n; m <<= 1, ++step, --l) {
-            ProfScope ps(c, "fft_stage");
-            const int np = (int)(m / 2 + 1);
-            {
-                ProfScope k(c, "fft_encode");
-                encode_batch(c, dre + off, dim + off, N / 2, np, p.sc[step], (int)l, work, P, dmx + off, 1);
-            }
-            fft_stage_core(c, Wa, P, Y, Z, Wb, (int)n, (int)n, (int)l, (int)(m / 2), 0, 2, np);
-            std::swap(Wa, Wb);
-            off += np;
-        }
-        if (inverse) {
-            ProfScope ps(c, "fft_stage");
-            fft_scale_step(c, Wa, P, Y, Z, Wb, (int)n, (int)l, (double)n, p.sc[step]);
-            std::swap(Wa, Wb);
-            --l;
-        }
-        std::vector<u64> mx(ntw);
-        if (ntw) HEC_HIP(hipMemcpyAsync(mx.data(), dmx, ntw * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
-        HEC_HIP(hipStreamSynchronize(c.stream));
-        off = 0;
-        for (std::size_t m = 2, ll = l0; m <= n; m <<= 1, --ll) {
-            fft_check_maxabs(c, mx.data() + off, m / 2 + 1, ll);
-            off += m / 2 + 1;
-        }
-        fft_store(c, Wa, out, n, l, p.sc[p.total]);
-    });
-}
-
-int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint64_t n, int inverse,
-             const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    return guard([&] {
-        set_device(ctx);
-        need(n <= ctx->c.N / 2 || (n & (n - 1)), "n must be at most slot_count");
-        const FftPlan p = FftPlan::make(ctx, in, B, n, inverse, out);
-        check_obj(ctx, gk, BAD_GK);
-        Ctx &c = ctx->c;
-        const std::size_t N = c.N, l0 = p.l0, S0 = 2 * l0 * N;
-        if (p.total == 0) {
-            for (uint64_t i = 0; i < B; ++i)
-                if (out[i] != in[i]) {
-                    grow(out[i], S0);
-                    d2d(c, out[i]->d, in[i]->d, S0);
-                    out[i]->size = 2; out[i]->level = l0; out[i]->scale = in[i]->scale;
-                }
-            return;
-        }
-        // the rotations of every stage (hec_rotate_vector_inplace's rule: one key, else the NAF terms), found before
-        // any work; diagonals of every stage, n values each, uploaded once
-        std::vector<std::vector<u32>> eltL(p.stages), eltR(p.stages);
-        std::vector<double> dre_h, dim_h;
-        std::vector<int> nterm(p.stages);
-        for (int i = 1; i <= p.stages; ++i) {
-            const uint64_t k = uint64_t(1) << i;
-            const int steps = (int)(n / k);
-            rotation_elts(c, steps, *gk, eltL[i - 1]);
-            if (i > 1) rotation_elts(c, -steps, *gk, eltR[i - 1]);
-            nterm[i - 1] = i > 1 ? 3 : 2;
-            for (int d = 0; d < nterm[i - 1]; ++d) {
-                const std::size_t o = dre_h.size();
-                dre_h.resize(o + n);
-                dim_h.resize(o + n);
-                need(hec_bfft_diagonal(d, k, n, inverse, &dre_h[o], &dim_h[o]) == HEC_OK, "n must be a power of two");
-            }
-        }
-        const std::size_t nd = dre_h.size(), nvec = nd / n;
-        encoder_tables(c);
-        // chunks of ciphertexts: one pass of 3 Bc x 2 x (l0 - 1) blocks
-        const std::size_t Bc = std::min<std::size_t>(B, std::max<std::size_t>(1, FFT_MAX_JOBS / (6 * l0)));
-        Scratch s(c, 6 * Bc * S0 + 3 * l0 * N + 6 * Bc * N + 6 * Bc * (l0 - 1) * N + 3 * 2 * N + 2 * nd + nvec +
-                         ks_words(c, Bc, l0) + 2 * Bc * l0 * N + 16 * 64);
-        u64 *Wa = s.take(3 * Bc * S0), *Wb = s.take(3 * Bc * S0), *P = s.take(3 * l0 * N), *Y = s.take(6 * Bc * N);
-        u64 *Z = s.take(std::max<std::size_t>(6 * Bc * (l0 - 1) * N, 1));
-        double *work = reinterpret_cast<double *>(s.take(3 * 2 * N));
-        double *dre = reinterpret_cast<double *>(s.take(nd)), *dim = reinterpret_cast<double *>(s.take(nd));
-        u64 *dmx = s.take(nvec);
-        HEC_HIP(hipMemcpyAsync(dre, dre_h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c.stream));
-        HEC_HIP(hipMemcpyAsync(dim, dim_h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c.stream));
-        std::vector<u64> mx(nvec);
-        for (std::size_t b0 = 0; b0 < B; b0 += Bc) {
-            const std::size_t cnt = std::min(Bc, B - b0);
-            for (std::size_t b = 0; b < cnt; ++b) d2d(c, Wa + b * S0, in[b0 + b]->d, S0);
-            std::size_t l = l0, off = 0;
-            for (int i = 1; i <= p.stages; ++i, --l) {
-                ProfScope ps(c, "bfft_stage");
-                const int nt = nterm[i - 1];
-                const u64 sb = 2 * (u64)l * N, sk = (u64)l * N;
-                {
-                    ProfScope k(c, "fft_encode");
-                    encode_batch(c, dre + off * n, dim + off * n, N / 2, nt, p.sc[i - 1], (int)l, work, P, dmx + off, n);
-                }
-                // the two rotations of the batch, back to back: entries [cnt, 2 cnt) and [2 cnt, 3 cnt) of the array
-                const PolyArr X{Wa, sb, sk};
-                for (int t = 1; t < nt; ++t) {
-                    const std::vector<u32> &elts = t == 1 ? eltL[i - 1] : eltR[i - 1];
-                    const PolyArr R{Wa + (u64)t * cnt * sb, sb, sk};
-                    for (std::size_t e = 0; e < elts.size(); ++e)
-                        galois_ks(c, s, e == 0 ? X : R, R, (int)cnt, (int)l, elts[e], gk->keys.at(elts[e]));
-                }
-                fft_stage_core(c, Wa, P, Y, Z, Wb, nt * (int)cnt, (int)cnt, (int)l, 0, (int)cnt, nt, nt);
-                std::swap(Wa, Wb);
-                off += nt;
-            }
-            if (inverse) {
-                ProfScope ps(c, "bfft_stage");
-                fft_scale_step(c, Wa, P, Y, Z, Wb, (int)cnt, (int)l, (double)n, p.sc[p.stages]);
-                std::swap(Wa, Wb);
-                --l;
-            }
-            if (b0 == 0) {
-                HEC_HIP(hipMemcpyAsync(mx.data(), dmx, nvec * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
-                HEC_HIP(hipStreamSynchronize(c.stream));
-                for (std::size_t v = 0, st = 0; st < (std::size_t)p.stages; ++st)
-                    for (int d = 0; d < nterm[st]; ++d, ++v) fft_check_maxabs(c, mx.data() + v, 1, l0 - st);
-            }
-            fft_store(c, Wa, out + b0, cnt, l, p.sc[p.total]);
-        }
-        HEC_HIP(hipStreamSynchronize(c.stream));  // the host diagonals go out of scope
-    });
-}
-
-// ------------------------------------------------------------------ he::math ---------------
-// signed_inv / inv_sqrt_twice / sqrt / abs (reference src/core/he_math.cpp:22-269) and he::util::drop_chain_levels on
-// a batch of ciphertexts of one level and scale.  Each schedule is written once, over MathRun, whose operations do the
-// host bookkeeping of the per-operation sequence (every scalar encode's checks, every product scale and its bound,
-// every division by q, every are_close, the end of the chain) in that sequence's order, and, when the run has a
-// device side, launch the stage over the whole batch.  A call walks its schedule twice: first without a device side
-// (the plan: the first failing check is the call's error, nothing has been written, and the peak number of live
-// iterates is known), then on the device.  hec_math_plan is the first walk alone.
-// Two stage kinds (hec_kernels.hip): the scalar stage OUT = rescale(A (*) c) +- d (math_lastprod, the batched INTT,
-// fft_round_limbs, math_cstage) and the product stage OUT = rescale(relin(A (*) (B' + d))) (math_tensor, then
-// keyswitch and rescale_batch as hec_matmul_finish runs them).  The iterates live in slots of one Scratch workspace.
-namespace {
-constexpr int MATH_MAX_JOBS = 65535;  // blocks along y of one NTT pass
-constexpr std::size_t MATH_AUTO_CHUNK = 256;  // automatic ciphertexts per pass at most (workspace size)
-
-// The product stage over B ciphertexts at level l: OUT = rescale(relin(A (*) (Bp [+ dw]))) at level l - 1.  A and Bp
-// may be one array (the squares); T3: 3 B l N words for the size-3 products.  he::math's products and
-// hec_multiply_relin_rescale_many (dw == nullptr) run it
-void product_stage(Ctx &c, Scratch &s, PolyArr A, PolyArr Bp, const u64 *dw, u64 *T3, const u64 *rk, int B, int l,
-                   PolyArr OUT)
-{
-    const u64 N = c.N, S3 = 3 * (u64)l * N;
-    const bool same = A.p == Bp.p;
-    {
-        ProfScope k(c, "k:k_math_tensor/math", ((same ? 2.0 : 4.0) + 3.0) * B * l);
-        math_tensor(c, A, Bp, dw, T3, B, l);
-    }
-    const PolyArr Aa{T3, S3, (u64)l * N};
-    keyswitch(c, s, PolyArr{T3 + 2 * (u64)l * N, S3, 0}, rk, Aa, 2, Aa, B, l);
-    rescale_batch(c, s, Aa, B, 2, l, OUT);
-}
-
-struct MathVal {
-    int slot = -1;
-    std::size_t level = 0;
-    double scale = 0;
-};
-
-struct MathRun {
-    Chain ch;
-    // device side; c == nullptr is the planning walk
-    Ctx *c = nullptr;
-    Scratch *s = nullptr;
-    const u64 *rk = nullptr;
-    int B = 0;
-    std::vector<u64 *> slot;
-    u64 *T3 = nullptr, *Y = nullptr, *Z = nullptr;
-    // slot bookkeeping, the same on both walks
-    std::vector<char> busy;
-    int peak = 0;
-
-    int take()
-    {
-        std::size_t i = 0;
-        while (i < busy.size() && busy[i]) ++i;
-        if (i == busy.size()) busy.push_back(0);
-        busy[i] = 1;
-        peak = std::max(peak, (int)i + 1);
-        return (int)i;
-    }
-    void drop(MathVal &v)
-    {
-        if (v.slot >= 0) busy[(std::size_t)v.slot] = 0;
-        v.slot = -1;
-    }
-    PolyArr arr(const MathVal &v) const
-    {
-        return PolyArr{slot[(std::size_t)v.slot], 2 * v.level * c->N, v.level * c->N};
-    }
-
-    // rescale(a (*) encode(cval, a.level, pscale)) [+- encode(dval) at the result's level and scale]: multiply_plain,
-    // rescale_to_next, add_plain / sub_plain.  dmode 0 none, 1 add, 2 subtract; pscale 0: a's own scale
-    MathVal cstage(const MathVal &a, double cval, int dmode = 0, double dval = 0, double pscale = 0)
-    {
-        const std::size_t l = a.level;
-        u64 cw[HEC_MAXL + 1], dw[HEC_MAXL + 1];
-        if (pscale == 0) pscale = a.scale;
-        scalar_words_chain(ch, cval, pscale, l, cw);
-        const double ns = a.scale * pscale;
-        need(ch.scale_ok(ns, l), "scale out of bounds");
-        if (l == 1) throw std::invalid_argument("end of modulus switching chain reached");
-        MathVal o;
-        o.level = l - 1;
-        o.scale = ns / (double)ch.q[l - 1];
-        if (dmode) {
-            scalar_words_chain(ch, dval, o.scale, o.level, dw);
-            need(are_close(o.scale, o.scale), "scale mismatch");  // add_plain's check; the plaintext has o's scale
-            if (dmode == 2)
-                for (std::size_t i = 0; i < o.level; ++i) dw[i] = dw[i] ? ch.q[i] - dw[i] : 0;
-        }
-        o.slot = take();
-        if (c) {
-            const u64 N = c->N, sb = 2 * l * N, sk = l * N;
-            const u64 *A = slot[(std::size_t)a.slot];
-            {
-                ProfScope k(*c, "k:k_math_lastprod/math", 4.0 * B);
-                math_lastprod(*c, A, sb, sk, Y, B, 2, (int)l, cw[l - 1]);
-            }
-            {
-                ProfScope k(*c, "k:k_ntt/math_intt", 8.0 * B, 2);
-                const int pm[1] = {(int)l - 1};
-                ntt_strided(*c, true, Y, N, Y, N, 1, pm, 2 * B);
-            }
-            {
-                ProfScope k(*c, "k:k_ntt/math_round_a", 2.0 * B * l);
-                fft_round_limbs(*c, Y, Z, B, 2, (int)l);
-            }
-            {  // Z, the source's data limbs and the outputs, once each
-                ProfScope k(*c, "k:k_ntt/math_cstage", 6.0 * B * (l - 1));
-                math_cstage(*c, Z, A, sb, sk, arr(o), B, 2, (int)l, cw, dmode ? dw : nullptr);
-            }
-        }
-        return o;
-    }
-
-    // rescale(relin(a (*) (b [+ encode(dval, b.level, b.scale)]))): add_plain, multiply / square, relinearize,
-    // rescale_to_next.  a and b may be one value (the square)
-    MathVal prod(const MathVal &a, const MathVal &b, bool has_d = false, double dval = 0)
-    {
-        u64 dw[HEC_MAXL + 1];
-        if (has_d) {
-            scalar_words_chain(ch, dval, b.scale, b.level, dw);
-            need(are_close(b.scale, b.scale), "scale mismatch");  // add_plain's check; the plaintext has b's scale
-        }
-        need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
-        const std::size_t l = a.level;
-        const double ns = a.scale * b.scale;
-        need(ch.scale_ok(ns, l), "scale out of bounds");
-        if (l == 1) throw std::invalid_argument("end of modulus switching chain reached");
-        MathVal o;
-        o.level = l - 1;
-        o.scale = ns / (double)ch.q[l - 1];
-        o.slot = take();
-        if (c) product_stage(*c, *s, arr(a), arr(b), has_d ? dw : nullptr, T3, rk, B, (int)l, arr(o));
-        return o;
-    }
-
-    // a - b into a's slot (sub_inplace)
-    void sub(MathVal &a, const MathVal &b)
-    {
-        need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
-        need(are_close(a.scale, b.scale), "scale mismatch");
-        if (c) ew_add(*c, arr(a), arr(b), arr(a), B, 2, (int)a.level, 1);
-    }
-
-    // he_math.cpp:22-90
-    MathVal signed_inv(const MathVal &x, double a, std::size_t iters)
-    {
-        MathVal y = cstage(x, -a * a, 1, 2 * a);
-        if (iters == 1) return y;
-        MathVal e = cstage(x, a, 2, 1.0);
-        MathVal t = cstage(y, 1.0, 0, 0, e.scale);  // y drops one level with the plaintext 1 encoded for e
-        drop(y);
-        y = t;
-        for (std::size_t i = 1; i < iters; ++i) {
-            t = prod(e, e);
-            drop(e);
-            e = t;
-            t = prod(y, e, true, 1.0);  // y (e^2 + 1)
-            drop(y);
-            y = t;
-        }
-        drop(e);
-        return y;
-    }
-
-    // he_math.cpp:95-164 (the `#if 1` form)
-    MathVal inv_sqrt_twice(const MathVal &x, double a, std::size_t iters)
-    {
-        const double y0 = a;
-        MathVal xl = x;  // x, dropped alongside the iterate; the caller's value is never released here
-        bool own = false;
-        MathVal y = cstage(x, -y0 * y0 * y0, 1, 3.0 / 2 * y0);
-        for (std::size_t i = 1; i < iters; ++i) {
-            MathVal yp = y;
-            MathVal t = cstage(yp, 3.0 / 2);
-            y = cstage(t, 1.0);
-            drop(t);
-            for (std::size_t j = 0; j < (i > 1 ? 2u : 1u); ++j) {
-                t = cstage(xl, 1.0);
-                if (own) drop(xl);
-                xl = t;
-                own = true;
-            }
-            MathVal xy = prod(xl, yp);
-            t = prod(yp, yp);
-            drop(yp);
-            yp = prod(t, xy);
-            drop(t);
-            drop(xy);
-            sub(y, yp);
-            drop(yp);
-        }
-        if (own) drop(xl);
-        return y;
-    }
-
-    // he_math.cpp:211-232; the level difference in size_t, as he::util::reach_chain_level takes it
-    MathVal sqrt(const MathVal &x, double a, std::size_t iters)
-    {
-        MathVal y = inv_sqrt_twice(x, 1 / a / std::sqrt(2), iters);
-        MathVal sv = cstage(x, std::sqrt(2));
-        const std::size_t n = (sv.level - 1) - (y.level - 1);
-        for (std::size_t k = 0; k < n; ++k) {
-            MathVal t = cstage(sv, 1.0);
-            drop(sv);
-            sv = t;
-        }
-        MathVal o = prod(y, sv);
-        drop(y);
-        drop(sv);
-        return o;
-    }
-
-    // he_math.cpp:237-269
-    MathVal abs(const MathVal &x, double a, std::size_t iters)
-    {
-        MathVal sq = prod(x, x);
-        MathVal y = inv_sqrt_twice(sq, 1 / a / std::sqrt(2), iters);
-        MathVal t = cstage(sq, std::sqrt(2));
-        drop(sq);
-        sq = t;
-        const std::size_t n = (sq.level - 1) - (y.level - 1);
-        for (std::size_t k = 0; k < n; ++k) {
-            t = cstage(sq, 1.0);
-            drop(sq);
-            sq = t;
-        }
-        MathVal o = prod(y, sq);
-        drop(y);
-        drop(sq);
-        return o;
-    }
-
-    // he_util.h:27-48
-    MathVal drop_levels(const MathVal &x, std::size_t levels)
-    {
-        MathVal v = x;
-        for (std::size_t k = 0; k < levels; ++k) {
-            MathVal t = cstage(v, 1.0);
-            if (k) drop(v);
-            v = t;
-        }
-        return v;
-    }
-
-    // fn: HEC_MATH_*, or -1 for drop_levels with iters levels.  The input occupies slot 0
-    MathVal run(int fn, double a, std::size_t iters, std::size_t level, double scale)
-    {
-        busy.assign(1, 1);
-        peak = 1;
-        MathVal x;
-        x.slot = 0;
-        x.level = level;
-        x.scale = scale;
-        switch (fn) {
-        case -1: return drop_levels(x, iters);
-        case HEC_MATH_SIGNED_INV: return signed_inv(x, a, iters);
-        case HEC_MATH_INV_SQRT_TWICE: return inv_sqrt_twice(x, a, iters);
-        case HEC_MATH_SQRT: return sqrt(x, a, iters);
-        case HEC_MATH_ABS: return abs(x, a, iters);
-        default: throw std::invalid_argument("unknown he::math function");
-        }
-    }
-};
-
-void math_batch(hec_context *ctx, int fn, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iters,
-                const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    need(ctx && x && out && B >= 1, "null argument");
-    set_device(ctx);
-    for (uint64_t i = 0; i < B; ++i) {
-        check_ct(ctx, x[i]);
-        check_obj(ctx, out[i], BAD_CT);
-        need(x[i]->size == 2, "encrypted size must be 2");
-        need(x[i]->level == x[0]->level, "encrypted1 and encrypted2 parameter mismatch");
-        need(std::memcmp(&x[i]->scale, &x[0]->scale, sizeof(double)) == 0, "scale mismatch");
-    }
-    if (fn >= 0) {
-        need(iters >= 1, "iter_num must be positive");
-        check_obj(ctx, rk, BAD_RK);
-    }
-    Ctx &c = ctx->c;
-    const std::size_t N = c.N, l0 = x[0]->level, S0 = 2 * l0 * N;
-    MathRun plan;
-    plan.ch = Chain{c.q.data(), c.L};
-    const MathVal res = plan.run(fn, a, iters, l0, x[0]->scale);
-    if (res.slot == 0) return;  // no level to drop: the inputs are the results
-    // ciphertexts per pass: the key switch's mod-up pass B runs Bc l0 l0 blocks along y
-    std::size_t Bc = std::min<std::size_t>(MATH_AUTO_CHUNK, std::max<std::size_t>(1, MATH_MAX_JOBS / ((l0 + 1) * l0)));
-    if (c.math_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.math_chunk);
-    Bc = std::min<std::size_t>(Bc, B);
-    const std::size_t nslot = (std::size_t)plan.peak;
-    Scratch s(c, nslot * Bc * S0 + Bc * 3 * l0 * N + 2 * Bc * N + 2 * Bc * l0 * N + ks_words(c, Bc, l0) +
-                     rescale_words(c, Bc, 2, l0) + (nslot + 16) * 64);
-    MathRun dev;
-    dev.ch = plan.ch;
-    dev.c = &c;
-    dev.s = &s;
-    dev.rk = rk ? rk->d : nullptr;
-    for (std::size_t i = 0; i < nslot; ++i) dev.slot.push_back(s.take(Bc * S0));
-    dev.T3 = s.take(Bc * 3 * l0 * N);
-    dev.Y = s.take(2 * Bc * N);
-    dev.Z = s.take(2 * Bc * l0 * N);
-    const std::size_t So = 2 * res.level * N;
-    for (std::size_t b0 = 0; b0 < B; b0 += Bc) {
-        const std::size_t cnt = std::min(Bc, B - b0);
-        dev.B = (int)cnt;
-        for (std::size_t b = 0; b < cnt; ++b) d2d(c, dev.slot[0] + b * S0, x[b0 + b]->d, S0);
-        const MathVal r = dev.run(fn, a, iters, l0, x[0]->scale);
-        for (std::size_t b = 0; b < cnt; ++b) {
-            hec_ciphertext *o = out[b0 + b];
-            grow(o, So);
-            d2d(c, o->d, dev.slot[(std::size_t)r.slot] + b * So, So);
-            o->size = 2;
-            o->level = r.level;
-            o->scale = r.scale;
-        }
-    }
-}
-}  // namespace
-
-int hec_math_plan(const uint64_t *coeff_modulus, uint64_t K, int fn, double a, uint64_t iter_num, uint64_t level,
-                  double scale, uint64_t *out_level, double *out_scale)
-{
-    return guard([&] {
-        need(coeff_modulus && out_level && out_scale, "null argument");
-        need(K >= 2 && K - 1 <= HEC_MAXL, "coeff_modulus size is not valid");
-        need(fn >= HEC_MATH_SIGNED_INV && fn <= HEC_MATH_ABS, "unknown he::math function");
-        need(level >= 1 && level <= K - 1, BAD_CT);
-        need(iter_num >= 1, "iter_num must be positive");
-        MathRun plan;
-        plan.ch = Chain{coeff_modulus, (std::size_t)(K - 1)};
-        const MathVal r = plan.run(fn, a, iter_num, level, scale);
-        *out_level = r.level;
-        *out_scale = r.scale;
-    });
-}
-
-int hec_math_signed_inv(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
-                        const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    return guard([&] { math_batch(ctx, HEC_MATH_SIGNED_INV, x, B, a, iter_num, rk, out); });
-}
-int hec_math_inv_sqrt_twice(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
-                            const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    return guard([&] { math_batch(ctx, HEC_MATH_INV_SQRT_TWICE, x, B, a, iter_num, rk, out); });
-}
-int hec_math_sqrt(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
-                  const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    return guard([&] { math_batch(ctx, HEC_MATH_SQRT, x, B, a, iter_num, rk, out); });
-}
-int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
-                 const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    return guard([&] { math_batch(ctx, HEC_MATH_ABS, x, B, a, iter_num, rk, out); });
-}
-int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels)
-{
-    return guard([&] { math_batch(ctx, -1, cts, B, 0.0, levels, nullptr, cts); });
-}
-
-// ------------------------------------------------------------------ he::linalg over many ciphertexts ------
-// Matrix::operator*=, BatchedMatrix::operator*= / square_inplace / sum_bvec_elems_inplace (reference
-// src/core/he_linalg.cpp) as stages over a batch.  The entries are grouped by level on the host (as dec_run groups
-// its inputs); a group's inputs are gathered into Scratch slots once, its stages run over the whole group (in passes
-// of at most 65,535 / ((l + 1) l) entries, as math_batch), and the outputs are scattered after the last stage.  Scales
-// are per entry and host bookkeeping only.
-namespace {
-struct LinalgPlan {  // class members: no C language linkage inside the C-ABI block
-// the rotation steps of BatchedVector::sum_elems_inplace (he_linalg.cpp:667-713) in order: to_sum's in-place
-// rotations by `window` and the accumulate rotations; dim = 1 rotates once and discards the result
-static std::vector<int> sum_elems_steps(uint64_t dim)
-{
-    need(dim >= 1, "dim must be positive");
-    need(dim < (1ull << 31), "step count too large");  // `window` is an int
-    std::vector<int> st;
-    int window = 1;
-    if (dim & 1) st.push_back(window);
-    for (uint64_t bits = dim >> 1; bits != 0; bits >>= 1) {
-        window <<= 1;
-        if (bits & 1) {
-            for (int steps = window >> 1; steps != 0; steps >>= 1) st.push_back(steps);
-            if (bits != 1) st.push_back(window);
-        }
-    }
-    return st;
-}
-
-// the caller's entries by level (ascending), the caller's order kept inside a level
-static std::map<std::size_t, std::vector<std::size_t>> by_level(const hec_ciphertext *const *x, uint64_t B)
-{
-    std::map<std::size_t, std::vector<std::size_t>> g;
-    for (uint64_t i = 0; i < B; ++i) g[x[i]->level].push_back(i);
-    return g;
-}
-};
-std::size_t linalg_chunk(const Ctx &c, std::size_t l, std::size_t n)
-{
-    std::size_t Bc = std::min<std::size_t>(MATH_AUTO_CHUNK, std::max<std::size_t>(1, MATH_MAX_JOBS / ((l + 1) * l)));
-    if (c.math_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.math_chunk);
-    return std::min(Bc, n);
-}
-// an output written by one pass must not be an input that a later pass gathers
-void check_out_alias(const std::vector<const hec_ciphertext *const *> &ins, hec_ciphertext *const *out, uint64_t B)
-{
-    std::map<const hec_ciphertext *, uint64_t> o;
-    for (uint64_t i = 0; i < B; ++i)
-        need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
-    for (const hec_ciphertext *const *in : ins)
-        for (uint64_t i = 0; i < B; ++i) {
-            const auto it = o.find(in[i]);
-            need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
-        }
-}
-void scatter(Ctx &c, hec_ciphertext *o, const u64 *src, std::size_t words, std::size_t level, double scale)
-{
-    grow(o, words);
-    d2d(c, o->d, src, words);
-    o->size = 2;
-    o->level = level;
-    o->scale = scale;
-}
-
-void product_many(hec_context *ctx, const hec_ciphertext *const *a, const hec_ciphertext *const *b, uint64_t B,
-                  const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    need(ctx != nullptr, "context is null");
-    if (B == 0) return;
-    need(a && b && out, "null argument");
-    set_device(ctx);
-    Ctx &c = ctx->c;
-    for (uint64_t i = 0; i < B; ++i) {  // multiply / square, relinearize, rescale_to_next on entry i
-        check_ct(ctx, a[i]);
-        check_ct(ctx, b[i]);
-        check_obj(ctx, out[i], BAD_CT);
-        need(a[i]->size == 2 && b[i]->size == 2, "encrypted size must be 2");
-        need(a[i]->level == b[i]->level, "encrypted1 and encrypted2 parameter mismatch");
-        need(scale_ok(c, a[i]->scale * b[i]->scale, a[i]->level), "scale out of bounds");
-        check_obj(ctx, rk, BAD_RK);
-        if (a[i]->level == 1) throw std::invalid_argument("end of modulus switching chain reached");
-    }
-    check_out_alias({a, b}, out, B);
-    const std::size_t N = c.N;
-    const auto groups = LinalgPlan::by_level(a, B);
-    std::size_t words = 0;
-    for (const auto &g : groups) {
-        const std::size_t l = g.first, Bc = linalg_chunk(c, l, g.second.size());
-        words = std::max(words, Bc * (2 * 2 * l * N + 2 * (l - 1) * N + 3 * l * N) + ks_words(c, Bc, l) +
-                                    rescale_words(c, Bc, 2, l) + 8 * 64);
-    }
-    Scratch s(c, words);
-    for (const auto &g : groups) {
-        const std::size_t l = g.first, S0 = 2 * l * N, So = 2 * (l - 1) * N, Bc = linalg_chunk(c, l, g.second.size());
-        s.top = 0;
-        u64 *A = s.take(Bc * S0), *Bp = s.take(Bc * S0), *O = s.take(Bc * So), *T3 = s.take(Bc * 3 * l * N);
-        for (std::size_t b0 = 0; b0 < g.second.size(); b0 += Bc) {
-            const std::size_t cnt = std::min(Bc, g.second.size() - b0);
-            bool same = true;
-            for (std::size_t k = 0; k < cnt; ++k) {
-                const std::size_t i = g.second[b0 + k];
-                d2d(c, A + k * S0, a[i]->d, S0);
-                same = same && a[i] == b[i];
-            }
-            if (!same)
-                for (std::size_t k = 0; k < cnt; ++k) d2d(c, Bp + k * S0, b[g.second[b0 + k]]->d, S0);
-            const PolyArr Aa{A, S0, l * N};
-            product_stage(c, s, Aa, same ? Aa : PolyArr{Bp, S0, l * N}, nullptr, T3, rk->d, (int)cnt, (int)l,
-                          PolyArr{O, So, (l - 1) * N});
-            for (std::size_t k = 0; k < cnt; ++k) {
-                const std::size_t i = g.second[b0 + k];
-                scatter(c, out[i], O + k * So, So, l - 1, a[i]->scale * b[i]->scale / (double)c.q[l - 1]);
-            }
-        }
-    }
-}
-
-void sum_elems_many(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, uint64_t dim,
-                    const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    need(ctx != nullptr, "context is null");
-    if (B == 0) return;
-    need(x && out, "null argument");
-    set_device(ctx);
-    Ctx &c = ctx->c;
-    const std::vector<int> plan = LinalgPlan::sum_elems_steps(dim);
-    std::map<int, u32> elt_of;
-    for (uint64_t i = 0; i < B; ++i) {  // the schedule's first rotation on entry i, then (once) the others' keys
-        check_ct(ctx, x[i]);
-        check_obj(ctx, out[i], BAD_CT);
-        check_obj(ctx, gk, BAD_GK);
-        need(x[i]->size == 2, "encrypted size must be 2");
-        if (i == 0)
-            for (int st : plan) {  // powers of two: no NAF decomposition stands in for an absent key
-                const u32 e = elt_from_step(c, st);
-                need(gk->keys.count(e) > 0, "Galois key not present");
-                elt_of[st] = e;
-            }
-        need(dim == 1 || are_close(x[i]->scale, x[i]->scale), "scale mismatch");  // the adds' check
-    }
-    check_out_alias({x}, out, B);
-    const std::size_t N = c.N;
-    const auto groups = LinalgPlan::by_level(x, B);
-    std::size_t words = 0;
-    for (const auto &g : groups) {
-        const std::size_t l = g.first, Bc = linalg_chunk(c, l, g.second.size());
-        words = std::max(words, 4 * Bc * 2 * l * N + 2 * Bc * l * N + ks_words(c, Bc, l) + 8 * 64);
-    }
-    Scratch s(c, words);
-    for (const auto &g : groups) {
-        const std::size_t l = g.first, S0 = 2 * l * N, Bc = linalg_chunk(c, l, g.second.size());
-        s.top = 0;
-        u64 *slot[4];
-        for (u64 *&p : slot) p = s.take(Bc * S0);
-        for (std::size_t b0 = 0; b0 < g.second.size(); b0 += Bc) {
-            const int cnt = (int)std::min(Bc, g.second.size() - b0);
-            for (int k = 0; k < cnt; ++k) d2d(c, slot[0] + k * S0, x[g.second[b0 + k]]->d, S0);
-            // bvec (r), to_sum (t) and partial (p) as slots; a rotation writes a free slot (its reads gather, so it
-            // cannot run in place), an accumulate step reads its addend at the words it writes
-            bool used[4] = {true, false, false, false};
-            auto arr = [&](int i) { return PolyArr{slot[i], S0, l * N}; };
-            auto fresh = [&] {
-                for (int i = 0; i < 4; ++i)
-                    if (!used[i]) { used[i] = true; return i; }
-                throw std::logic_error("sum_elems: no free slot");
-            };
-            // dst = rotate(src, st) [+ add]
-            auto rot = [&](int src, int st, int add) {
-                const int dst = fresh();
-                const u32 e = elt_of.at(st);
-                galois_ks(c, s, arr(src), arr(dst), cnt, (int)l, e, gk->keys.at(e), add >= 0 ? arr(add) : PolyArr{});
-                return dst;
-            };
-            int r = 0, t = 0, p = -1;
-            bool have = false;
-            int window = 1;
-            if (dim & 1) {
-                have = true;
-                if (dim != 1) t = rot(t, window, -1);  // dim = 1: the reference discards this rotation
-            }
-            for (uint64_t bits = dim >> 1; bits != 0; bits >>= 1) {
-                window <<= 1;
-                if (!(bits & 1)) continue;
-                int steps = window >> 1;
-                int acc = rot(t, steps, t);  // acc = to_sum + (to_sum << steps)
-                if (!have && r != t) used[r] = false;
-                for (steps >>= 1; steps != 0; steps >>= 1) {  // acc += acc << steps
-                    const int n = rot(acc, steps, acc);
-                    used[acc] = false;
-                    acc = n;
-                }
-                if (have) {
-                    p = acc;
-                    ProfScope k(c, "k:k_ew_add/sum", 6.0 * cnt * l);
-                    ew_add(c, arr(r), arr(p), arr(r), cnt, 2, (int)l, 0);
-                    used[p] = false;
-                } else {
-                    r = acc;
-                    have = true;
-                }
-                if (bits != 1) {
-                    const int n = rot(t, window, -1);
-                    if (t != r) used[t] = false;
-                    t = n;
-                }
-            }
-            for (int k = 0; k < cnt; ++k) {
-                const std::size_t i = g.second[b0 + k];
-                scatter(c, out[i], slot[r] + k * S0, S0, l, x[i]->scale);
-            }
-        }
-    }
-}
-}  // namespace
-
-int hec_multiply_relin_rescale_many(hec_context *ctx, const hec_ciphertext *const *a, const hec_ciphertext *const *b,
-                                    uint64_t B, const hec_kswitch_key *rk, hec_ciphertext *const *out)
-{
-    return guard([&] { product_many(ctx, a, b, B, rk, out); });
-}
-int hec_sum_elems_many(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, uint64_t dim,
-                       const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    return guard([&] { sum_elems_many(ctx, x, B, dim, gk, out); });
-}
-int hec_sum_elems_plan(uint64_t dim, int *steps, uint64_t cap, uint64_t *count)
-{
-    return guard([&] {
-        need(count != nullptr && (steps != nullptr || cap == 0), "null argument");
-        const std::vector<int> st = LinalgPlan::sum_elems_steps(dim);
-        *count = st.size();
-        for (std::size_t i = 0; i < st.size() && i < cap; ++i) steps[i] = st[i];
+        for (uint64_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, sc[i]);
     });
 }
 
@@ -4672,14 +3639,8 @@ int hec_matmul_col_colT(hec_context *ctx, const hec_ciphertext *const *A, uint64
         };
         auto no_flush = [](const u64 *) {};
         walk_trie(c, s, trie, 0, Ba, 0, (int)n, (int)l, *gk, bufs, S2, visit, no_flush);
-        const PolyArr Ca{AC, S3, l * N};
-        keyswitch(c, s, PolyArr{AC + 2 * l * N, S3, 0}, rk->d, Ca, 2, Ca, (int)p, (int)l);
-        rescale_batch(c, s, Ca, (int)p, 2, (int)l, PolyArr{O, So, (l - 1) * N});
-        for (uint64_t i = 0; i < p; ++i) {
-            grow(out[i], So);
-            d2d(c, out[i]->d, O + i * So, So);
-            out[i]->size = 2; out[i]->level = l - 1; out[i]->scale = sc / (double)c.q[l - 1];
-        }
+        relin_rescale(c, s, AC, rk->d, (int)p, (int)l, PolyArr{O, So, (l - 1) * N});
+        for (uint64_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, sc / (double)c.q[l - 1]);
     });
 }
 
@@ -4732,14 +3693,8 @@ int hec_matrix_matmul(hec_context *ctx, const hec_ciphertext *const *A, uint64_t
                 }
             }
         (void)one;
-        const PolyArr Ca{AC, S3, l * N};
-        keyswitch(c, s, PolyArr{AC + 2 * l * N, S3, 0}, rk->d, Ca, 2, Ca, (int)no, (int)l);
-        rescale_batch(c, s, Ca, (int)no, 2, (int)l, PolyArr{O, So, (l - 1) * N});
-        for (uint64_t o = 0; o < no; ++o) {
-            grow(out[o], So);
-            d2d(c, out[o]->d, O + o * So, So);
-            out[o]->size = 2; out[o]->level = l - 1; out[o]->scale = sc[o] / (double)c.q[l - 1];
-        }
+        relin_rescale(c, s, AC, rk->d, (int)no, (int)l, PolyArr{O, So, (l - 1) * N});
+        for (uint64_t o = 0; o < no; ++o) store_ct(c, out[o], O + o * So, 2, l - 1, sc[o] / (double)c.q[l - 1]);
     });
 }
 

@@ -1,0 +1,121 @@
+"""Record the launch ledger tests/golden/launch_ledger.json: for a fixed list of engine calls, every profile class the
+call touches with its number of scopes, its kernel launches and its algorithmic bytes.  The ledger is recorded at the
+commit BEFORE a change that must not alter the launch sequence and checked after it (tests/test_gpu_launch_ledger.py).
+
+Only the Python binding is used: the inputs and the keys come from the engine's uniform fills, so nothing is checked
+about the words here.  Each call runs once unprofiled (the first-use tables are built), then once under profile(2).
+
+Usage (on the GPU): python tests/golden/make_launch_ledger.py [--out tests/golden/launch_ledger.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+FIXTURE = os.path.join(HERE, "launch_ledger.json")
+sys.path.insert(0, os.path.join(HERE, ".."))
+
+N = 1 << 11
+BITS = [60, 40, 40, 40, 40, 60]
+LEVEL = 4
+SCALE = 2.0**40
+STEPS = (1, 2, 4, 8, -1, -2, -4)
+
+
+class Env:
+    def __init__(self, hecdna):
+        self.ctx = hecdna.Context(N, hecdna.create_coeff_modulus(N, BITS))
+        self.rk = self.ctx.relin_key(seed=11)
+        self.gk = self.ctx.galois_keys(uniform_elts=[self.ctx.elt_from_step(s) for s in STEPS], seed=5)
+        self.seed = 100
+
+    def cts(self, count, level=LEVEL, size=2, scale=SCALE):
+        out = []
+        for _ in range(count):
+            self.seed += 1
+            out.append(self.ctx.ciphertext().fill_uniform(size, level, scale, self.seed))
+        return out
+
+
+def _chunked(fn):
+    def run(e):
+        e.ctx.set_option("math_chunk", 2)
+        try:
+            fn(e)
+        finally:
+            e.ctx.set_option("math_chunk", 0)
+    return run
+
+
+def _partial_finish(e):
+    A, X = e.cts(10), e.cts(2)
+    acc = e.ctx.matmul_diag_col_partial(A, 0, 10, X, e.gk)
+    e.ctx.matmul_finish(acc, e.rk)
+
+
+def _mixed_product(e):
+    a = e.cts(2) + e.cts(1, level=3)
+    b = e.cts(2) + e.cts(1, level=3)
+    e.ctx.multiply_relin_rescale(a, b, e.rk)
+
+
+def _square(e):
+    a = e.cts(3)
+    e.ctx.multiply_relin_rescale(a, a, e.rk)
+
+
+# name -> call; the inputs are made inside the call (fills carry no profile scope)
+CALLS = {
+    "sum_elems_B3_dim7": lambda e: e.ctx.sum_elems(e.cts(3), 7, e.gk),
+    "sum_elems_B3_dim8": lambda e: e.ctx.sum_elems(e.cts(3), 8, e.gk),
+    "sum_elems_B1_dim1": lambda e: e.ctx.sum_elems(e.cts(1), 1, e.gk),
+    "product_B3_levels_4_4_3": _mixed_product,
+    "product_square_B3": _square,
+    "product_square_B3_chunk2": _chunked(_square),
+    "signed_inv_B2_iters1": lambda e: e.ctx.signed_inv(e.cts(2), 1.0, 1, e.rk),
+    "signed_inv_B2_iters2": lambda e: e.ctx.signed_inv(e.cts(2), 1.0, 2, e.rk),
+    "abs_B2_iters1": lambda e: e.ctx.abs(e.cts(2), 1.0, 1, e.rk),
+    "drop_chain_levels_B2_by1": lambda e: e.ctx.drop_chain_levels(e.cts(2), 1),
+    "fft_n4": lambda e: e.ctx.fft(e.cts(4)),
+    "bfft_B2_n4_inverse": lambda e: e.ctx.bfft(e.cts(2), 4, e.gk, inverse=True),
+    "matmul_diag_col_n10_p2": lambda e: e.ctx.matmul_diag_col(e.cts(10), e.cts(2), e.rk, e.gk),
+    "matmul_partial_then_finish_n10_p2": _partial_finish,
+    "matmul_col_colT_n6_p5": lambda e: e.ctx.matmul_col_colT(e.cts(6), e.cts(6), 5, e.rk, e.gk),
+    "matrix_matmul_2x2": lambda e: e.ctx.matrix_matmul(e.cts(4), 2, 2, 0, e.cts(4), 2, 2, 0, e.rk),
+    "relinearize_inplace": lambda e: e.ctx.relinearize(e.cts(1, size=3)[0], e.rk),
+    "rescale_to_next_inplace": lambda e: e.ctx.rescale_to_next(e.cts(1)[0]),
+}
+
+
+def record(hecdna):
+    """{call: {class: [scopes, kernel_launches, alg_bytes]}} on a fresh context"""
+    e = Env(hecdna)
+    ledger = {}
+    for name, call in CALLS.items():
+        call(e)
+        e.ctx.profile(2)
+        try:
+            call(e)
+            ledger[name] = {}
+            for cls in e.ctx.profile_classes():
+                _, scopes, nbytes, launches = e.ctx.profile_read_ex(cls)
+                ledger[name][cls] = [scopes, launches, nbytes]
+        finally:
+            e.ctx.profile(0)
+    e.ctx.close()
+    return ledger
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=FIXTURE)
+    args = ap.parse_args()
+    import torch
+    torch.cuda.is_available()  # one HIP runtime for torch and the engine (tests/conftest.py)
+    from _helpers import load_hecdna
+    led = record(load_hecdna())
+    with open(args.out, "w") as f:
+        json.dump(led, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{len(led)} calls, {sum(len(v) for v in led.values())} classes -> {args.out}")
