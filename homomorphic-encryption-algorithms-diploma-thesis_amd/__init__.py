@@ -99,6 +99,8 @@ def lib():
             "hec_apply_galois_inplace": [vp, vp, C.c_uint32, vp],
             "hec_matmul_diag_col": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp],
             "hec_matmul_diagpt_col": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp],
+            "hec_bsgs_plan": [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint64, u64p, u64p],
+            "hec_matmul_diagpt_col_bsgs": [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp],
             "hec_plaintext_fill_uniform": [vp, C.c_uint64, C.c_double, C.c_uint64],
             "hec_plaintext_download": [vp, u64p],
             "hec_plaintext_info": [vp, u64p, C.POINTER(C.c_double)],
@@ -504,6 +506,30 @@ def sum_elems_plan(dim, cap=None):
     return list(buf[:min(int(cap), n.value)]), n.value
 
 
+def bsgs_plan(n, bs=None):
+    """hec_bsgs_plan (host only): (bs_eff, steps) of Context.matmul_diagpt_col_bsgs for an n x n matrix: the baby
+    steps 1 .. bs_eff - 1, then the giant steps g * bs_eff.  bs=None picks the smallest power of two >= sqrt(n).  A key
+    set with exactly these steps' elements makes every rotation one key switch."""
+    cnt, eff = C.c_uint64(), C.c_uint64()
+    b = 0 if bs is None else int(bs)
+    if bs is not None and b < 1:
+        raise InvalidArgument(HEC_EINVAL, "bs must be positive")
+    _check(lib().hec_bsgs_plan(int(n), b, None, 0, C.byref(cnt), C.byref(eff)))
+    buf = (C.c_int * max(1, cnt.value))()
+    _check(lib().hec_bsgs_plan(int(n), b, buf, cnt.value, C.byref(cnt), C.byref(eff)))
+    return eff.value, list(buf[:cnt.value])
+
+
+def bsgs_diagonals(diag_values, bs=None):
+    """The BSGS form of n diagonals given as [n][slots] slot vectors (row j: diagonal j over all slots): row j rotated
+    right by (j // bs_eff) * bs_eff slots, the vectors Context.matmul_diagpt_col_bsgs expects encoded."""
+    d = np.asarray(diag_values)
+    if d.ndim != 2:
+        raise InvalidArgument(HEC_EINVAL, "diag_values must be [n][slots]")
+    eff, _ = bsgs_plan(d.shape[0], bs)
+    return np.stack([np.roll(d[j], (j // eff) * eff) for j in range(d.shape[0])])
+
+
 def create_coeff_modulus(N, bits):
     out = np.zeros(len(bits), dtype=np.uint64)
     _check(lib().hec_create_coeff_modulus(N, (C.c_int * len(bits))(*bits), len(bits), _p(out)))
@@ -789,6 +815,19 @@ class Context:
         out = out or [Ciphertext(self) for _ in cols]
         _check(lib().hec_matmul_diagpt_col(self.h, self._arr(pdiags), len(pdiags), self._arr(cols), len(cols), gk.h,
                                            self._arr(out)))
+        return out
+
+    def matmul_diagpt_col_bsgs(self, pdiags, cols, gk, bs=None, out=None):
+        """hec_matmul_diagpt_col_bsgs: the ct x pt matvec from (bs_eff - 1) + (ceil(n / bs_eff) - 1) rotations.  pdiags
+        are the encodings of bsgs_diagonals(...) for the same bs.  Decrypts to matmul_diagpt_col's product; its
+        ciphertext bits are those of the per-operation composition in the schedule's order, not the reference
+        loop's (they coincide for bs >= n)."""
+        out = out or [Ciphertext(self) for _ in cols]
+        b = 0 if bs is None else int(bs)
+        if bs is not None and b < 1:
+            raise InvalidArgument(HEC_EINVAL, "bs must be positive")
+        _check(lib().hec_matmul_diagpt_col_bsgs(self.h, self._arr(pdiags), len(pdiags), b, self._arr(cols), len(cols),
+                                                gk.h, self._arr(out)))
         return out
 
     def matmul_diag_col_partial(self, diags, j_begin, j_end, cols, gk, out=None):

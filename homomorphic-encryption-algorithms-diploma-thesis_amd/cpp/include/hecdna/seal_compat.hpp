@@ -833,4 +833,39 @@ private:
     const Context *ctx_;
 };
 
+// The ct x pt matvec on the baby-step giant-step schedule (hec_matmul_diagpt_col_bsgs; the reference has no ct x pt
+// matrix class to mirror, so this is a free function over the C call): pdiags are the n plaintext diagonals in BSGS
+// form (diagonal j's slot vector rotated right by (j / bs_eff) bs_eff slots before encoding), bs = 0 the default block
+// size.  One output per column, rescaled.  The product of the reference loop (he_linalg.cpp:943-1006 with
+// multiply_plain, he_operators.cpp:128-142) from (bs_eff - 1) + (ceil(n / bs_eff) - 1) rotations; NOT its ciphertext
+// bits unless bs_eff = n.  bsgs_steps() lists the rotation steps whose Galois keys make each rotation one key switch.
+inline std::vector<int> bsgs_steps(std::size_t n, std::size_t bs = 0, std::size_t *bs_eff = nullptr)
+{
+    std::uint64_t count = 0, eff = 0;
+    check(hec_bsgs_plan(n, bs, nullptr, 0, &count, &eff));
+    std::vector<int> steps(count);
+    check(hec_bsgs_plan(n, bs, steps.data(), count, &count, &eff));
+    if (bs_eff) *bs_eff = eff;
+    return steps;
+}
+inline std::vector<Ciphertext> matmul_diagpt_col_bsgs(const Evaluator &eval, const std::vector<Plaintext> &pdiags,
+                                                      const std::vector<Ciphertext> &cols, const GaloisKeys &gk,
+                                                      std::size_t bs = 0)
+{
+    std::vector<const hec_plaintext *> pp;
+    std::vector<const hec_ciphertext *> pc;
+    for (const auto &p : pdiags) pp.push_back(p.get());
+    for (const auto &c : cols) pc.push_back(c.get());
+    std::vector<Ciphertext> out;
+    std::vector<hec_ciphertext *> po;
+    out.reserve(cols.size());
+    for (std::size_t i = 0; i < cols.size(); ++i) {
+        out.emplace_back(eval.context());
+        po.push_back(out.back().get());
+    }
+    check(hec_matmul_diagpt_col_bsgs(eval.context().get(), pp.data(), pp.size(), bs, pc.data(), pc.size(), gk.get(),
+                                     po.data()));
+    return out;
+}
+
 }  // namespace hecdna

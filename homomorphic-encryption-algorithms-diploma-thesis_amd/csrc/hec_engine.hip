@@ -792,6 +792,13 @@ struct TrieBufs {
         for (int d = 0; d <= depth; ++d)
             for (int k = 0; k < (d == 0 ? 1 : nb); ++k) b[d].push_back(s.take(words));
     }
+    // per[d] buffers at depth d: with per[d] = the trie's nodes at depth d, every node keeps its own buffer for the
+    // whole walk (the baby rotations of bsgs_core stay alive until the inner kernel has read them)
+    TrieBufs(Scratch &s, const std::vector<int> &per, u64 words) : b(per.size()), next(per.size(), 0)
+    {
+        for (std::size_t d = 0; d < per.size(); ++d)
+            for (int k = 0; k < per[d]; ++k) b[d].push_back(s.take(words));
+    }
     u64 *take(int d) { return b[d][next[d]++ % b[d].size()]; }
 };
 
@@ -1117,6 +1124,202 @@ void matvec_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec
     else relin_rescale(c, s, ACC3, rk->d, (int)p, (int)l, Oa, "relin");
     const double ql = (double)c.q[l - 1];
     for (std::size_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, ps[i] / ql);
+}
+
+// ---------------------------------------------------------------- baby-step giant-step ct x pt matvec
+// The same product over another schedule (opt-in, not the bits of matvec_core unless bs_eff = n):
+//   inner_g = sum_{i < bs, g bs + i < n} multiply_plain(rotate_vector(x, i), P'[g bs + i])
+//   out     = rescale_to_next(inner_0 + sum_{1 <= g < G} rotate_vector(inner_g, g bs))
+// with the plaintext diagonals in BSGS form (P'[j] encodes diagonal j rotated right by (j / bs) bs slots), so
+// (bs - 1) + (G - 1) rotations stand for the n - 1 of the reference loop.  Every operation is the per-operation
+// call's (rotate_vector as rotation_elts() flattens it, multiply_plain's reduced products, exact modular sums), so
+// the words equal that composition's.
+struct BsgsPlan {
+    std::size_t bs = 0, G = 0;  // bs_eff and the giant groups
+    std::vector<int> steps;     // the rotation steps in the order the call issues them: babies, then giants
+};
+BsgsPlan bsgs_plan(uint64_t n, uint64_t bs)
+{
+    need(n >= 1, "empty matrix operand");
+    need(n < (1ull << 30), "step count too large");  // the steps are ints
+    if (bs == 0)
+        for (bs = 1; bs * bs < n;) bs <<= 1;  // the smallest power of two >= sqrt(n)
+    BsgsPlan p;
+    p.bs = (std::size_t)std::min<uint64_t>(bs, n);
+    need(p.bs <= 1024, "bs must be at most 1024");  // k_bsgs_inner's exact FP64 sums (hec_kernels.hip)
+    p.G = (n + p.bs - 1) / p.bs;
+    for (std::size_t i = 1; i < p.bs; ++i) p.steps.push_back((int)i);
+    for (std::size_t g = 1; g < p.G; ++g) p.steps.push_back((int)(g * p.bs));
+    return p;
+}
+
+// matvec_check's checks in its order over the BSGS schedule's operations, all before anything is written; returns the
+// product scale of every output
+std::vector<double> bsgs_check(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
+                               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk,
+                               hec_ciphertext *const *out)
+{
+    const Ctx &c = ctx->c;
+    need(p >= 1, "empty matrix operand");
+    check_obj(ctx, gk, BAD_GK);
+    for (std::size_t i = 0; i < p; ++i) check_ct(ctx, cols[i]);
+    const std::size_t l = cols[0]->level;
+    for (std::size_t i = 0; i < p; ++i) need(cols[i]->size == 2, "encrypted size must be 2");
+    for (std::size_t i = 0; i < p; ++i) need(cols[i]->level == l, "encrypted1 and encrypted2 parameter mismatch");
+    for (std::size_t j = 0; j < n; ++j) check_plain_data(ctx, pdiags[j]);
+    for (std::size_t j = 0; j < n; ++j) need(pdiags[j]->level == l, "encrypted_ntt and plain_ntt parameter mismatch");
+    {  // out[i] may be cols[i]; an output that is another entry's input, or listed twice, is refused
+        std::map<const hec_ciphertext *, std::size_t> o;
+        for (std::size_t i = 0; i < p; ++i) {
+            check_obj(ctx, out[i], BAD_CT);
+            need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
+        }
+        for (std::size_t i = 0; i < p; ++i) {
+            const auto it = o.find(cols[i]);
+            need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
+        }
+    }
+    std::vector<double> ps(p);
+    for (std::size_t i = 0; i < p; ++i)
+        for (std::size_t j = 0; j < n; ++j) {
+            const double sc = cols[i]->scale * pdiags[j]->scale;
+            need(scale_ok(c, sc, l), "scale out of bounds");
+            if (j == 0) ps[i] = sc;
+            else need(are_close(ps[i], sc), "scale mismatch");
+        }
+    if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
+    std::vector<u32> seq;  // rotate_internal's own errors over every planned step
+    for (int st : plan.steps) {
+        seq.clear();
+        rotation_elts(c, st, *gk, seq);
+    }
+    return ps;
+}
+
+void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
+               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    Ctx &c = ctx->c;
+    const std::vector<double> ps = bsgs_check(ctx, pdiags, n, plan, cols, p, gk, out);
+    const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
+    const std::size_t GG = (std::size_t)bsgs_tile(c);
+    // baby phase: the trie of rotate(x, i), i < bs, every node with a buffer of its own
+    RotTrie trie;
+    std::vector<std::vector<u32>> gelts(G);  // giant g's key switches
+    {
+        std::vector<u32> seq;
+        for (std::size_t i = 0; i < bs; ++i) {
+            seq.clear();
+            rotation_elts(c, (int)i, *gk, seq);
+            trie.insert(seq, i);
+        }
+        for (std::size_t g = 1; g < G; ++g) rotation_elts(c, (int)(g * bs), *gk, gelts[g]);
+    }
+    const int D = trie.depth;
+    std::vector<int> per((std::size_t)D + 1, 0), depth_of(trie.nodes.size(), 0);
+    per[0] = 1;
+    for (std::size_t nd = 0; nd < trie.nodes.size(); ++nd)  // a child's index follows its parent's
+        for (int ch : trie.nodes[nd].children) ++per[(std::size_t)(depth_of[(std::size_t)ch] = depth_of[nd] + 1)];
+    const std::size_t nbuf = trie.nodes.size();
+    const bool hoist = c.hoist && D > 0;
+    const u64 S2 = 2 * l * N, So = 2 * (l - 1) * N;
+    auto words_for = [&](std::size_t Bc) {
+        std::size_t w = Bc * (S2 * (nbuf + GG + 2) + So) + 2 * Bc * l * N + ks_words(c, Bc, l) +
+                        rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
+        if (hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
+        return w;
+    };
+    // input vectors per pass: the y-blocks of the key switch's mod-up launch ((l + 1) l per vector), option
+    // "bsgs_chunk", and a workspace that fits the free device memory
+    std::size_t Bc = std::min<std::size_t>({p, 256, std::max<std::size_t>(1, 65535 / ((l + 1) * l))});
+    if (c.bsgs_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.bsgs_chunk);
+    if (words_for(Bc) > c.ws.words) {
+        std::size_t fr = 0, tot = 0;
+        HEC_HIP(hipMemGetInfo(&fr, &tot));
+        while (Bc > 1 && words_for(Bc) > c.ws.words && (double)words_for(Bc) * 8.0 > 0.9 * (double)fr) Bc = (Bc + 1) / 2;
+    }
+    Scratch s(c, words_for(Bc));
+    std::vector<const u64 *> hp(n), hr(bs);
+    for (std::size_t j = 0; j < n; ++j) hp[j] = pdiags[j]->d;
+    const u64 **tabP = reinterpret_cast<const u64 **>(s.take(n));
+    const u64 **tabR = reinterpret_cast<const u64 **>(s.take(bs));
+    HEC_HIP(hipMemcpyAsync(tabP, hp.data(), n * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
+    hec_galois_keys &gkm = const_cast<hec_galois_keys &>(*gk);  // the lazily built per-key tables are caches
+    if (hoist)
+        for (std::size_t nd = 1; nd < trie.nodes.size(); ++nd) {
+            galois_negw(ctx, gkm, trie.nodes[nd].elt);
+            galois_kw(ctx, gkm, trie.nodes[nd].elt, (int)l);
+            if (c.hmac_cfg != 0) galois_mkey(ctx, gkm, trie.nodes[nd].elt);
+        }
+    const std::size_t mark = s.top;
+    const double ql = (double)c.q[l - 1];
+    for (std::size_t b0 = 0; b0 < p; b0 += Bc) {
+        const std::size_t cnt = std::min(Bc, p - b0);
+        s.top = mark;  // every carve of a pass is sized by its own count (the hoisted accumulators are contiguous)
+        TrieBufs bufs(s, per, cnt * S2);
+        u64 *A[2] = {s.take(cnt * S2), s.take(cnt * S2)};
+        std::vector<u64 *> T(GG);
+        for (std::size_t t = 0; t < GG; ++t) T[t] = s.take(cnt * S2);
+        u64 *O = s.take(cnt * So);
+        std::vector<Hoist> hs((std::size_t)D);
+        if (hoist)
+            for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
+        for (std::size_t i = 0; i < cnt; ++i) d2d(c, bufs.b[0][0] + i * S2, cols[b0 + i]->d, S2);
+        const PolyArr Xa{bufs.b[0][0], S2, l * N};
+        auto visit = [&](std::size_t i, PolyArr src) { hr[i] = src.p; };
+        auto keep = [](const u64 *) {};  // no buffer is written twice in a walk
+        auto babies = [&](bool hoisted) {
+            std::fill(bufs.next.begin(), bufs.next.end(), 0u);
+            if (hoisted) {
+                dev_zero(c, c.zflag, 2 * sizeof(int));
+                walk_trie_hoisted(c, s, trie, 0, Xa, 0, (int)cnt, (int)l, ctx, gkm, bufs, hs, S2, c.hoist_min_children,
+                                  visit, keep);
+            } else {
+                walk_trie(c, s, trie, 0, Xa, 0, (int)cnt, (int)l, *gk, bufs, S2, visit, keep);
+            }
+            HEC_HIP(hipMemcpyAsync(tabR, hr.data(), bs * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
+        };
+        babies(hoist);
+        int zfl[2] = {0, 0};
+        if (hoist) HEC_HIP(hipMemcpyAsync(zfl, c.zflag, 2 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));  // the flag is read; the pointer table has left the host vector
+        if (zfl[0]) {  // a digit limb with more zero coefficients than the hoisted MAC corrects: the babies again
+            if (std::getenv("HEC_DEBUG"))
+                std::fprintf(stderr, "hec: zero-list overflow, baby rotations recomputed without hoisting (p=%zu)\n", cnt);
+            babies(false);
+            HEC_HIP(hipStreamSynchronize(c.stream));
+        }
+        // inner and giant phases over tiles of GG giants: only one tile of inner sums is live; inner_0 starts the
+        // accumulator, every other inner_g is rotated by g bs with the accumulator added in the key switch's last stage
+        int cur = 0;
+        for (std::size_t g0 = 0; g0 < G; g0 += GG) {
+            const std::size_t ng = std::min(GG, G - g0);
+            BsgsInner a{};
+            a.R = tabR; a.P = tabP; a.n = n; a.bs = (int)bs; a.g0 = (int)g0; a.ng = (int)ng;
+            for (std::size_t t = 0; t < ng; ++t) a.out[t] = g0 + t == 0 ? A[cur] : T[t];
+            {
+                ProfScope pr(c, "bsgs_inner");
+                // the babies once per launch (2 B l each), the tile's plaintexts once (l each), the outputs once
+                const double npt = (double)(std::min(n, (g0 + ng) * bs) - g0 * bs);
+                ProfScope k(c, "k:k_bsgs_inner", 2.0 * cnt * l * (double)(bs + ng) + npt * l);
+                bsgs_inner(c, a, S2, l * N, S2, l * N, (int)cnt, (int)l);
+            }
+            for (std::size_t t = 0; t < ng; ++t) {
+                const std::size_t g = g0 + t;
+                if (g == 0) continue;
+                const PolyArr X{T[t], S2, l * N};
+                const std::vector<u32> &el = gelts[g];
+                for (std::size_t e = 0; e + 1 < el.size(); ++e)
+                    galois_ks(c, s, X, X, (int)cnt, (int)l, el[e], gk->keys.at(el[e]));
+                galois_ks(c, s, X, PolyArr{A[1 - cur], S2, l * N}, (int)cnt, (int)l, el.back(), gk->keys.at(el.back()),
+                          PolyArr{A[cur], S2, l * N});
+                cur = 1 - cur;
+            }
+        }
+        rescale_batch(c, s, PolyArr{A[cur], S2, l * N}, (int)cnt, 2, (int)l, PolyArr{O, So, (l - 1) * N});
+        for (std::size_t i = 0; i < cnt; ++i) store_ct(c, out[b0 + i], O + i * So, 2, l - 1, ps[b0 + i] / ql);
+    }
+    HEC_HIP(hipStreamSynchronize(c.stream));  // the host pointer tables go out of scope
 }
 
 
@@ -1834,6 +2037,13 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "prng_group") c.prng_group = in(0, 16);
             else if (n == "math_chunk") c.math_chunk = in(0, 65535);
             else if (n == "rot_add") c.rot_add = in(0, 1);
+            else if (n == "bsgs_chunk") c.bsgs_chunk = in(0, 65535);
+            else if (n == "bsgs_bg" || n == "bsgs_gg") {
+                const bool bg = n == "bsgs_bg";
+                if (!(value == 2 || value == 4 || (bg ? value == 1 : value == 8 || value == 16)))
+                    throw std::invalid_argument("option " + n + (bg ? " takes 1, 2 or 4" : " takes 2, 4, 8 or 16"));
+                (bg ? c.bsgs_bg : c.bsgs_gg) = (int)value;
+            } else if (n == "bsgs_order") c.bsgs_order = in(0, 1);
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -3415,6 +3625,28 @@ int hec_matmul_diagpt_col(hec_context *ctx, const hec_plaintext *const *diags, u
         std::vector<std::size_t> js(n);
         for (std::size_t j = 0; j < n; ++j) js[j] = j;
         matvec_lanes(ctx, nullptr, diags, n, js, cols, p, nullptr, gk, true, out);
+    });
+}
+
+int hec_bsgs_plan(uint64_t n, uint64_t bs, int *steps, uint64_t cap, uint64_t *count, uint64_t *bs_eff)
+{
+    return guard([&] {
+        need(count != nullptr && (steps != nullptr || cap == 0), "null argument");
+        const BsgsPlan plan = bsgs_plan(n, bs);
+        *count = plan.steps.size();
+        if (bs_eff) *bs_eff = plan.bs;
+        for (std::size_t i = 0; i < plan.steps.size() && i < cap; ++i) steps[i] = plan.steps[i];
+    });
+}
+
+int hec_matmul_diagpt_col_bsgs(hec_context *ctx, const hec_plaintext *const *pdiags, uint64_t n, uint64_t bs,
+                               const hec_ciphertext *const *cols, uint64_t p, const hec_galois_keys *gk,
+                               hec_ciphertext *const *out)
+{
+    return guard([&] {
+        set_device(ctx);
+        need(pdiags && cols && out, "null argument");
+        bsgs_core(ctx, pdiags, n, bsgs_plan(n, bs), cols, p, gk, out);
     });
 }
 

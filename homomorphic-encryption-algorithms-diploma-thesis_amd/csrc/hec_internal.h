@@ -151,6 +151,12 @@ struct Ctx {
                                    // k_ew_add launch after it.  Same words
     int math_chunk = 0;            // option "math_chunk": ciphertexts per pass of the he::math calls, 0 automatic (the
                                    // 65,535 y-blocks of an NTT launch bound it).  Every value computes the same words
+    int bsgs_chunk = 0;            // option "bsgs_chunk": input vectors per pass of hec_matmul_diagpt_col_bsgs, 0 automatic
+                                   // (the NTT launches' y-blocks and the free device memory bound it).  Same words
+    int bsgs_bg = 2, bsgs_gg = 8;  // options "bsgs_bg", "bsgs_gg": k_bsgs_inner's tile, batch entries x giant groups
+                                   // per thread (the instantiations of bsgs_inner()).  Same words
+    int bsgs_order = 1;            // option "bsgs_order": 1 k_bsgs_inner's batch groups of a coefficient block on
+                                   // consecutive block ids, 0 coefficient blocks consecutive.  Same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -280,6 +286,19 @@ struct TensorBatch {
 };
 void tensor_multi(Ctx &c, const TensorBatch &tb, u64 r_sb, u64 r_sk, u64 a_sk, PolyArr ACC, int B, int l,
                   bool assign, bool plain = false);  // plain: the A_t are plaintexts (ct x pt, 2-poly ACC)
+// the inner sums of the baby-step giant-step ct x pt matvec (k_bsgs_inner): giants g0 .. g0 + ng - 1, ng <=
+// bsgs_tile(c); out[t][b][k] = sum_i P[(g0 + t) bs + i] R[i][b][k] over the babies i < bs with (g0 + t) bs + i < n.
+// R (bs pointers) and P (n pointers) are device tables; R[i][b] at R[i] + b r_sb, polys r_sk apart; out likewise
+constexpr int BSGS_GG_MAX = 16;
+struct BsgsInner {
+    const u64 *const *R;
+    const u64 *const *P;
+    u64 *out[BSGS_GG_MAX];
+    u64 n;
+    int bs, g0, ng;
+};
+int bsgs_tile(const Ctx &c);  // giants per k_bsgs_inner launch (option "bsgs_gg")
+void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int l);
 void tensor_sum(Ctx &c, PolyArr R, PolyArr A, u64 *ACC, u64 acc_sk, int B, int l);
 void ew_add(Ctx &c, PolyArr a, PolyArr b, PolyArr out, int B, int nk, int nl, int mode);  // 0 add, 1 sub
 void ew_negate(Ctx &c, PolyArr a, int B, int nk, int nl);

@@ -3903,6 +3903,140 @@ void tensor_multi(Ctx &c, const TensorBatch &tb, u64 r_sb, u64 r_sk, u64 a_sk, P
     HEC_HIP(hipGetLastError());
 }
 
+// The inner sums of the baby-step giant-step ct x pt matvec (hec_engine.hip bsgs_core) for a tile of ng <= GG giant
+// groups g0 .. g0 + ng - 1 in one launch:
+//   OUT_t[b][k] = sum_{i < bs, (g0 + t) bs + i < n} P'[(g0 + t) bs + i] R_i[b][k] mod q,   k in {0, 1}
+// R_i = rotate(x, i) (R_0 = x), the same bs rotations for every giant.  A thread owns one coefficient of BG batch
+// entries and the tile's giants: per baby it loads the 2 BG rotation words once and the (up to) GG plaintext words once
+// and keeps 2 BG GG accumulators, so a launch reads every baby rotation once (not once per giant) and every plaintext
+// word once per batch group.  The arithmetic is k_tensor_multi2<PT = true>'s: FP64 primes sum exact fp_mulmod products
+// (|.| <= 0.53 q) as integer-valued doubles (bs <= 1024 terms, q < 2^42: |sum| < 2^52) and canonicalise once; 60-bit
+// primes reduce every product (mulmod) and add mod q.  Every multiply_plain product is thus reduced as SEAL reduces
+// it and the sums are exact, so the words equal the per-operation composition's.
+// The rotation and plaintext pointers (bs + n separate allocations) come from device tables built once per call.
+// order 1: the batch groups of one coefficient block take consecutive block ids, so the blocks that read the same
+// plaintext words run together (the words come from L2 / MALL after their first read); order 0: coefficient blocks
+// consecutive, as k_tensor_multi2's plain grid.
+template <int BG, int GG>
+__global__ void __launch_bounds__(256)
+    k_bsgs_inner(BsgsInner a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int logN, u64 total,
+                 const DevPrime *__restrict__ primes, int nbg, int ncb, int order)
+{
+    const u32 id = blockIdx.x;
+    const int cb = order ? (int)(id / (u32)nbg) : (int)(id % (u32)ncb);
+    const int bgi = order ? (int)(id % (u32)nbg) : (int)(id / (u32)ncb);
+    const u64 idx = (u64)cb * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int b0 = bgi * BG;
+    if (b0 >= B) return;
+    const int nb = min(BG, B - b0);
+    const int ng = min(GG, a.ng);
+    const DevPrime pr = primes[idx >> logN];
+    u64 d0[GG][BG], d1[GG][BG];
+    if (pr.fp) {
+        double s0[GG][BG], s1[GG][BG];
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) s0[t][g] = s1[t][g] = 0;
+        for (int i = 0; i < a.bs; ++i) {
+            const u64 *r = a.R[i] + (u64)b0 * r_sb + idx;
+            double r0[BG], r1[BG];
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                const bool on = g < nb;
+                r0[g] = on ? u2d(r[g * r_sb]) : 0.0;
+                r1[g] = on ? u2d(r[g * r_sb + r_sk]) : 0.0;
+            }
+#pragma unroll
+            for (int t = 0; t < GG; ++t) {
+                const u64 j = (u64)(a.g0 + t) * (u64)a.bs + (u64)i;
+                if (t >= ng || j >= a.n) break;  // only the last giant group is partial
+                const double pw = u2d(a.P[j][idx]);
+#pragma unroll
+                for (int g = 0; g < BG; ++g) {
+                    s0[t][g] += fp_mulmod(r0[g], pw, pr.qd, pr.qinv);
+                    s1[t][g] += fp_mulmod(r1[g], pw, pr.qd, pr.qinv);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                d0[t][g] = fp_canon(s0[t][g], pr.qd, pr.qinv);
+                d1[t][g] = fp_canon(s1[t][g], pr.qd, pr.qinv);
+            }
+    } else {
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) d0[t][g] = d1[t][g] = 0;
+        for (int i = 0; i < a.bs; ++i) {
+            const u64 *r = a.R[i] + (u64)b0 * r_sb + idx;
+            u64 r0[BG], r1[BG];
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                const bool on = g < nb;
+                r0[g] = on ? r[g * r_sb] : 0;
+                r1[g] = on ? r[g * r_sb + r_sk] : 0;
+            }
+#pragma unroll
+            for (int t = 0; t < GG; ++t) {
+                const u64 j = (u64)(a.g0 + t) * (u64)a.bs + (u64)i;
+                if (t >= ng || j >= a.n) break;
+                const u64 pw = a.P[j][idx];
+#pragma unroll
+                for (int g = 0; g < BG; ++g) {
+                    d0[t][g] = addmod(d0[t][g], mulmod(r0[g], pw, pr), pr.q);
+                    d1[t][g] = addmod(d1[t][g], mulmod(r1[g], pw, pr), pr.q);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < GG; ++t) {
+        if (t >= ng) break;
+        u64 *o = a.out[t] + (u64)b0 * o_sb + idx;
+#pragma unroll
+        for (int g = 0; g < BG; ++g) {
+            if (g >= nb) break;
+            o[g * o_sb] = d0[t][g];
+            o[g * o_sb + o_sk] = d1[t][g];
+        }
+    }
+}
+
+int bsgs_tile(const Ctx &c) { return c.bsgs_gg; }
+
+void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int l)
+{
+    if (a.ng < 1 || a.ng > c.bsgs_gg || a.bs < 1 || B < 1) throw std::logic_error("bsgs_inner: bad tile");
+    const u64 total = (u64)l * c.N;
+    const int BG = c.bsgs_bg, ncb = (int)((total + 255) / 256), nbg = (B + BG - 1) / BG;
+    const dim3 grid((unsigned)((u64)ncb * (u64)nbg));
+#define HEC_BSGS(BGv, GGv)                                                                                         \
+    k_bsgs_inner<BGv, GGv><<<grid, 256, 0, c.stream>>>(a, r_sb, r_sk, o_sb, o_sk, B, c.logN, total, c.primes, nbg, \
+                                                       ncb, c.bsgs_order)
+    switch (BG * 32 + c.bsgs_gg) {
+    case 1 * 32 + 2: HEC_BSGS(1, 2); break;
+    case 1 * 32 + 4: HEC_BSGS(1, 4); break;
+    case 1 * 32 + 8: HEC_BSGS(1, 8); break;
+    case 1 * 32 + 16: HEC_BSGS(1, 16); break;
+    case 2 * 32 + 2: HEC_BSGS(2, 2); break;
+    case 2 * 32 + 4: HEC_BSGS(2, 4); break;
+    case 2 * 32 + 8: HEC_BSGS(2, 8); break;
+    case 2 * 32 + 16: HEC_BSGS(2, 16); break;
+    case 4 * 32 + 2: HEC_BSGS(4, 2); break;
+    case 4 * 32 + 4: HEC_BSGS(4, 4); break;
+    case 4 * 32 + 8: HEC_BSGS(4, 8); break;
+    case 4 * 32 + 16: HEC_BSGS(4, 16); break;
+    default: throw std::logic_error("bsgs_inner: no kernel for this tile");
+    }
+#undef HEC_BSGS
+    HEC_HIP(hipGetLastError());
+}
+
 // ACC (size 3) = sum_b R[b] (x) A[b]  (col x col^T form: one output, the batch is the j-sum)
 __global__ void __launch_bounds__(256)
     k_tensor_sum(PolyArr R, PolyArr A, u64 *__restrict__ ACC, u64 acc_sk, int B, int logN, u64 total,

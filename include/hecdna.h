@@ -287,6 +287,35 @@ int hec_matmul_diag_col_partial_set(hec_context *ctx, const hec_ciphertext *cons
 int hec_matmul_diagpt_col(hec_context *ctx, const hec_plaintext *const *diags, uint64_t n,
                           const hec_ciphertext *const *cols, uint64_t p, const hec_galois_keys *gk,
                           hec_ciphertext *const *out);
+/* The rotation steps of the baby-step giant-step ct x pt matvec below (host only, no context): the babies
+ * 1 .. bs_eff - 1, then the giants g bs_eff for 1 <= g < ceil(n / bs_eff), with bs_eff = min(bs, n); bs = 0 picks the
+ * smallest power of two >= sqrt(n).  A caller with a key for exactly these steps (hec_keygen_galois over their
+ * elements) pays one key switch per step: (bs_eff - 1) + (ceil(n / bs_eff) - 1) against the n - 1 rotations, each
+ * a NAF chain, of BatchedMatrix::matmul's loop (he_linalg.cpp:943-1006; `*= eval % plain` is multiply_plain_inplace,
+ * he_operators.cpp:128-142).  The schedule is not the reference's, so its ciphertext bits are not either.
+ * *count = the number of steps, min(cap, *count) of them written to steps; *bs_eff (optional) = bs_eff.
+ * HEC_EINVAL for n = 0, n >= 2^30 and bs_eff > 1024. */
+int hec_bsgs_plan(uint64_t n, uint64_t bs, int *steps, uint64_t cap, uint64_t *count, uint64_t *bs_eff);
+/* ct x pt matvec on the baby-step giant-step schedule: the product of hec_matmul_diagpt_col (he_linalg.cpp:943-1006
+ * with multiply_plain, he_operators.cpp:128-142) from (bs_eff - 1) + (G - 1) rotations, G = ceil(n / bs_eff):
+ *   inner_g = sum_{i < bs_eff, g bs_eff + i < n} multiply_plain(rotate_vector(cols[c], i), pdiags[g bs_eff + i])
+ *   out[c]  = rescale_to_next( inner_0 + sum_{1 <= g < G} rotate_vector(inner_g, g bs_eff) )
+ * pdiags are in BSGS form: pdiags[j] encodes diagonal j's slot vector rotated right by (j / bs_eff) bs_eff slots.
+ * NOT bit-identical to hec_matmul_diagpt_col unless bs_eff = n (it decrypts to the same product); it IS word for
+ * word, with level and scale, what the per-operation calls above give when composed in this order, rotate_vector by
+ * SEAL's rule (the step's own key, else its NAF chain).  Every check (objects, sizes, levels, scales, "end of
+ * modulus switching chain reached", "Galois key not present" over every step of hec_bsgs_plan) comes before the
+ * first write.  out[c] may be cols[c]; an output that is another entry's input, or listed twice, is HEC_EINVAL.
+ * A pass of Bc input vectors holds (nodes + GG + 2) Bc ciphertexts of workspace beside the key switch's own: nodes =
+ * the nodes of the baby rotations' prefix trie (bs_eff with a key per step, more on a sparser key set such as the
+ * default one, whose NAF chains pass through steps outside 0 .. bs_eff - 1), GG = "bsgs_gg".  Bc is halved until that
+ * fits the free device memory; when not even one vector fits, the call fails with HEC_EDEVICE (an allocation error).
+ * Runs on the context's stream in passes of at most "bsgs_chunk" input vectors (option, 0..65535, 0 = automatic);
+ * the outputs do not depend on it, nor on "bsgs_bg" (1, 2, 4), "bsgs_gg" (2, 4, 8, 16) and "bsgs_order" (0..1), the
+ * inner-sum kernel's tile and grid order.  Batch lanes and the sharded path do not take this route. */
+int hec_matmul_diagpt_col_bsgs(hec_context *ctx, const hec_plaintext *const *pdiags, uint64_t n, uint64_t bs,
+                               const hec_ciphertext *const *cols, uint64_t p, const hec_galois_keys *gk,
+                               hec_ciphertext *const *out);
 /* relinearize + rescale a batch of size-3 accumulators (he_linalg.cpp:999-1002) */
 int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, const hec_kswitch_key *rk,
                       hec_ciphertext *const *out);
