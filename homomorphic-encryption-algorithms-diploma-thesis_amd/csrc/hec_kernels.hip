@@ -1533,13 +1533,17 @@ struct FanModUpT {  // source (b, J) = D[b][J] (inverse pass-B domain) -> E[b][I
     // 10 q_I over all stages and every output is canonicalised): a digit with q_J <= 2 q_I needs no
     // reduction at all, only the conversion
     // sdbl: the source (an FP64-class digit, q_J < 2^42) is held as the bits of its canonical integer-valued double,
-    // converted once per block instead of once per FP64 target; the two integer targets convert it back
+    // converted once per block instead of once per FP64 target; the two integer targets convert it back.  An FP64
+    // target takes it unreduced whatever q_J / q_I is (42-bit digit, 30-bit target: 2^12): fp_mulmod's bound is on
+    // |y| itself (3 |y| 2^-53 in k, hec_device.h), and |y| < q_J + 16 x 0.53 q_I < 2^45.4 for any two primes below
+    // 2^42, every intermediate an integer below 2^53, fp_canon's |x| < 2^52 included
+    // (tests/test_prime_classes.py test_forward_model_unreduced_wide_digit, the ALLFP chain of the GPU suite)
     __device__ void xf16(const Tgt &t, bool fp, const u64 *d, const u32 *, u64 *v, bool sdbl = false) const
     {
         if (sdbl) {
             if (fp) {
 #pragma unroll
-                for (int k = 0; k < 16; ++k) v[k] = d[k];  // q_J < 2 q_I: no reduction (see above)
+                for (int k = 0; k < 16; ++k) v[k] = d[k];  // |y| < q_J < 2^42: no reduction (see above)
                 return;
             }
 #pragma unroll

@@ -28,10 +28,10 @@ def tol_of(v, N):
 class DEnv:
     """Oracle + GPU context + one secret key on both sides (no key-switching keys anywhere)."""
 
-    def __init__(self, orc, hecdna, logN):
+    def __init__(self, orc, hecdna, logN, bits=None):
         self.orc, self.hec = orc, hecdna
         self.N = 1 << logN
-        self.m = orc.Oracle.create_coeff_modulus(self.N, BITS[logN])
+        self.m = orc.Oracle.create_coeff_modulus(self.N, bits or BITS[logN])
         self.L = len(self.m) - 1
         self.o = orc.Oracle(self.N, self.m)
         self.ctx = hecdna.Context(self.N, self.m)

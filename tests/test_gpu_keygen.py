@@ -32,10 +32,10 @@ def seed(tag: str) -> bytes:
 
 
 class KEnv:
-    def __init__(self, orc, hecdna, logN, pure=False, q0=None):
+    def __init__(self, orc, hecdna, logN, pure=False, q0=None, bits=None):
         self.orc, self.hec = orc, hecdna
         self.N = 1 << logN
-        self.m = orc.Oracle.create_coeff_modulus(self.N, BITS)
+        self.m = orc.Oracle.create_coeff_modulus(self.N, bits or BITS)
         if q0:
             self.m[0] = q0
         self.o = orc.Oracle(self.N, self.m)
