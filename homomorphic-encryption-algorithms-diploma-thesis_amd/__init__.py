@@ -101,6 +101,7 @@ def lib():
             "hec_matmul_diagpt_col": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp],
             "hec_bsgs_plan": [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint64, u64p, u64p],
             "hec_matmul_diagpt_col_bsgs": [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp],
+            "hec_matmul_diag_col_bsgs": [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp, vp],
             "hec_plaintext_fill_uniform": [vp, C.c_uint64, C.c_double, C.c_uint64],
             "hec_plaintext_download": [vp, u64p],
             "hec_plaintext_info": [vp, u64p, C.POINTER(C.c_double)],
@@ -828,6 +829,32 @@ class Context:
             raise InvalidArgument(HEC_EINVAL, "bs must be positive")
         _check(lib().hec_matmul_diagpt_col_bsgs(self.h, self._arr(pdiags), len(pdiags), b, self._arr(cols), len(cols),
                                                 gk.h, self._arr(out)))
+        return out
+
+    def matmul_diag_col_bsgs(self, diags, cols, rk, gk, bs=None, out=None):
+        """hec_matmul_diag_col_bsgs: the ct x ct matvec from (bs_eff - 1) baby rotations, ceil(n / bs_eff)
+        relinearisations and as many giant rotations less one.  diags encrypt the rows of bsgs_diagonals(...) for the
+        same bs (or come from bsgs_rotate_diagonals).  Decrypts to matmul_diag_col's product; its ciphertext bits are
+        those of the per-operation composition in the schedule's order, not the reference loop's (they coincide for
+        bs >= n).  bs_eff is at most 512."""
+        out = out or [Ciphertext(self) for _ in cols]
+        b = 0 if bs is None else int(bs)
+        if bs is not None and b < 1:
+            raise InvalidArgument(HEC_EINVAL, "bs must be positive")
+        _check(lib().hec_matmul_diag_col_bsgs(self.h, self._arr(diags), len(diags), b, self._arr(cols), len(cols),
+                                              rk.h, gk.h, self._arr(out)))
+        return out
+
+    def bsgs_rotate_diagonals(self, diags, bs, gk):
+        """The BSGS form of a matrix whose ciphertext diagonals arrive in natural form: copies of diags with diags[j]
+        rotated right by (j // bs_eff) * bs_eff slots (rotate_vector by the negative step, so gk needs keys for the
+        negative giant steps or their NAF chains).  Once per matrix, one rotation at a time; every rotation adds
+        key-switch noise to its diagonal, which bsgs_diagonals before encryption does not."""
+        eff, _ = bsgs_plan(len(diags), bs)
+        out = [d.copy() for d in diags]
+        for j, d in enumerate(out):
+            if j // eff:
+                self.rotate_vector(d, -(j // eff) * eff, gk)
         return out
 
     def matmul_diag_col_partial(self, diags, j_begin, j_end, cols, gk, out=None):

@@ -868,4 +868,41 @@ inline std::vector<Ciphertext> matmul_diagpt_col_bsgs(const Evaluator &eval, con
     return out;
 }
 
+// The ct x ct matvec on the same schedule (hec_matmul_diag_col_bsgs): the product of BatchedMatrix::matmul diag x col
+// (he_linalg.cpp:943-1006) from (bs_eff - 1) baby rotations, G = ceil(n / bs_eff) relinearisations and G - 1 giant
+// rotations; diags are the n ciphertext diagonals in BSGS form, bs_eff <= 512.  NOT the reference loop's ciphertext
+// bits unless bs_eff = n.
+inline std::vector<Ciphertext> matmul_diag_col_bsgs(const Evaluator &eval, const std::vector<Ciphertext> &diags,
+                                                    const std::vector<Ciphertext> &cols, const RelinKeys &rk,
+                                                    const GaloisKeys &gk, std::size_t bs = 0)
+{
+    std::vector<const hec_ciphertext *> pd, pc;
+    for (const auto &d : diags) pd.push_back(d.get());
+    for (const auto &c : cols) pc.push_back(c.get());
+    std::vector<Ciphertext> out;
+    std::vector<hec_ciphertext *> po;
+    out.reserve(cols.size());
+    for (std::size_t i = 0; i < cols.size(); ++i) {
+        out.emplace_back(eval.context());
+        po.push_back(out.back().get());
+    }
+    check(hec_matmul_diag_col_bsgs(eval.context().get(), pd.data(), pd.size(), bs, pc.data(), pc.size(), rk.get(),
+                                   gk.get(), po.data()));
+    return out;
+}
+// The BSGS form of a matrix whose ciphertext diagonals arrive in natural form: diags[j] rotated right by
+// (j / bs_eff) bs_eff slots, one rotate_vector at a time.  Once per matrix; gk needs the negative giant steps (or
+// their NAF chains), and every rotation adds key-switch noise to its diagonal, which rolling the slot vectors before
+// encryption does not.
+inline std::vector<Ciphertext> bsgs_rotate_diagonals(const Evaluator &eval, const std::vector<Ciphertext> &diags,
+                                                     std::size_t bs, const GaloisKeys &gk)
+{
+    std::size_t eff = 0;
+    bsgs_steps(diags.size(), bs, &eff);
+    std::vector<Ciphertext> out(diags);
+    for (std::size_t j = 0; j < out.size(); ++j)
+        if (j / eff) eval.rotate_vector_inplace(out[j], -(int)((j / eff) * eff), gk);
+    return out;
+}
+
 }  // namespace hecdna

@@ -1196,41 +1196,41 @@ std::vector<double> bsgs_check(hec_context *ctx, const hec_plaintext *const *pdi
     return ps;
 }
 
-void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
-               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    Ctx &c = ctx->c;
-    const std::vector<double> ps = bsgs_check(ctx, pdiags, n, plan, cols, p, gk, out);
-    const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
-    const std::size_t GG = (std::size_t)bsgs_tile(c);
-    // baby phase: the trie of rotate(x, i), i < bs, every node with a buffer of its own
+// The rotations of a BSGS call, shared by the ct x pt and the ct x ct form: the trie of rotate(x, i), i < bs, every
+// node with a buffer of its own (per[d] nodes at depth d), and giant g's key switches
+struct BsgsRots {
     RotTrie trie;
-    std::vector<std::vector<u32>> gelts(G);  // giant g's key switches
-    {
-        std::vector<u32> seq;
-        for (std::size_t i = 0; i < bs; ++i) {
-            seq.clear();
-            rotation_elts(c, (int)i, *gk, seq);
-            trie.insert(seq, i);
-        }
-        for (std::size_t g = 1; g < G; ++g) rotation_elts(c, (int)(g * bs), *gk, gelts[g]);
+    std::vector<std::vector<u32>> gelts;
+    std::vector<int> per;
+    int D = 0;
+    bool hoist = false;
+};
+BsgsRots bsgs_rots(const Ctx &c, const BsgsPlan &plan, const hec_galois_keys &gk)
+{
+    BsgsRots r;
+    r.gelts.resize(plan.G);
+    std::vector<u32> seq;
+    for (std::size_t i = 0; i < plan.bs; ++i) {
+        seq.clear();
+        rotation_elts(c, (int)i, gk, seq);
+        r.trie.insert(seq, i);
     }
-    const int D = trie.depth;
-    std::vector<int> per((std::size_t)D + 1, 0), depth_of(trie.nodes.size(), 0);
-    per[0] = 1;
-    for (std::size_t nd = 0; nd < trie.nodes.size(); ++nd)  // a child's index follows its parent's
-        for (int ch : trie.nodes[nd].children) ++per[(std::size_t)(depth_of[(std::size_t)ch] = depth_of[nd] + 1)];
-    const std::size_t nbuf = trie.nodes.size();
-    const bool hoist = c.hoist && D > 0;
-    const u64 S2 = 2 * l * N, So = 2 * (l - 1) * N;
-    auto words_for = [&](std::size_t Bc) {
-        std::size_t w = Bc * (S2 * (nbuf + GG + 2) + So) + 2 * Bc * l * N + ks_words(c, Bc, l) +
-                        rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
-        if (hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
-        return w;
-    };
-    // input vectors per pass: the y-blocks of the key switch's mod-up launch ((l + 1) l per vector), option
-    // "bsgs_chunk", and a workspace that fits the free device memory
+    for (std::size_t g = 1; g < plan.G; ++g) rotation_elts(c, (int)(g * plan.bs), gk, r.gelts[g]);
+    r.D = r.trie.depth;
+    std::vector<int> depth_of(r.trie.nodes.size(), 0);
+    r.per.assign((std::size_t)r.D + 1, 0);
+    r.per[0] = 1;
+    for (std::size_t nd = 0; nd < r.trie.nodes.size(); ++nd)  // a child's index follows its parent's
+        for (int ch : r.trie.nodes[nd].children) ++r.per[(std::size_t)(depth_of[(std::size_t)ch] = depth_of[nd] + 1)];
+    r.hoist = c.hoist && r.D > 0;
+    return r;
+}
+
+// input vectors per pass: the y-blocks of the key switch's mod-up launch ((l + 1) l per vector), option
+// "bsgs_chunk", and a workspace (words_for(Bc) words) that fits the free device memory
+template <class W>
+std::size_t bsgs_pass_size(const Ctx &c, std::size_t p, std::size_t l, W words_for)
+{
     std::size_t Bc = std::min<std::size_t>({p, 256, std::max<std::size_t>(1, 65535 / ((l + 1) * l))});
     if (c.bsgs_chunk > 0) Bc = std::min<std::size_t>(Bc, (std::size_t)c.bsgs_chunk);
     if (words_for(Bc) > c.ws.words) {
@@ -1238,6 +1238,76 @@ void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t
         HEC_HIP(hipMemGetInfo(&fr, &tot));
         while (Bc > 1 && words_for(Bc) > c.ws.words && (double)words_for(Bc) * 8.0 > 0.9 * (double)fr) Bc = (Bc + 1) / 2;
     }
+    return Bc;
+}
+
+// the per-key tables of the hoisted baby walk (lazily built caches of gk)
+void bsgs_key_tables(hec_context *ctx, const BsgsRots &r, hec_galois_keys &gkm, std::size_t l)
+{
+    if (!r.hoist) return;
+    for (std::size_t nd = 1; nd < r.trie.nodes.size(); ++nd) {
+        galois_negw(ctx, gkm, r.trie.nodes[nd].elt);
+        galois_kw(ctx, gkm, r.trie.nodes[nd].elt, (int)l);
+        if (ctx->c.hmac_cfg != 0) galois_mkey(ctx, gkm, r.trie.nodes[nd].elt);
+    }
+}
+
+// One pass's baby phase: cols[b0 .. b0 + cnt) into the root's buffer, the trie walked (hoisted; again without hoisting
+// when a digit limb has more zero coefficients than the hoisted MAC corrects), rotation i's buffer in hr[i] and the
+// table uploaded to tabR.  Returns with the stream synchronised: the pointer table has left the host vector.
+void bsgs_babies(hec_context *ctx, Scratch &s, const BsgsRots &r, hec_galois_keys &gkm, TrieBufs &bufs,
+                 const std::vector<Hoist> &hs, const hec_ciphertext *const *cols, std::size_t cnt, std::size_t l,
+                 std::vector<const u64 *> &hr, const u64 **tabR)
+{
+    Ctx &c = ctx->c;
+    const u64 S2 = 2 * l * c.N;
+    for (std::size_t i = 0; i < cnt; ++i) d2d(c, bufs.b[0][0] + i * S2, cols[i]->d, S2);
+    const PolyArr Xa{bufs.b[0][0], S2, l * c.N};
+    auto visit = [&](std::size_t i, PolyArr src) { hr[i] = src.p; };
+    auto keep = [](const u64 *) {};  // no buffer is written twice in a walk
+    auto babies = [&](bool hoisted) {
+        std::fill(bufs.next.begin(), bufs.next.end(), 0u);
+        if (hoisted) {
+            dev_zero(c, c.zflag, 2 * sizeof(int));
+            walk_trie_hoisted(c, s, r.trie, 0, Xa, 0, (int)cnt, (int)l, ctx, gkm, bufs, hs, S2, c.hoist_min_children,
+                              visit, keep);
+        } else {
+            walk_trie(c, s, r.trie, 0, Xa, 0, (int)cnt, (int)l, gkm, bufs, S2, visit, keep);
+        }
+        HEC_HIP(hipMemcpyAsync(tabR, hr.data(), hr.size() * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
+    };
+    babies(r.hoist);
+    int zfl[2] = {0, 0};
+    if (r.hoist) HEC_HIP(hipMemcpyAsync(zfl, c.zflag, 2 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HEC_HIP(hipStreamSynchronize(c.stream));  // the flag is read; the pointer table has left the host vector
+    if (zfl[0]) {
+        if (std::getenv("HEC_DEBUG"))
+            std::fprintf(stderr, "hec: zero-list overflow, baby rotations recomputed without hoisting (p=%zu)\n", cnt);
+        babies(false);
+        HEC_HIP(hipStreamSynchronize(c.stream));
+    }
+}
+
+void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
+               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    Ctx &c = ctx->c;
+    const std::vector<double> ps = bsgs_check(ctx, pdiags, n, plan, cols, p, gk, out);
+    const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
+    const std::size_t GG = (std::size_t)bsgs_tile(c);
+    const BsgsRots rots = bsgs_rots(c, plan, *gk);
+    const std::vector<std::vector<u32>> &gelts = rots.gelts;
+    const int D = rots.D;
+    const std::size_t nbuf = rots.trie.nodes.size();
+    const bool hoist = rots.hoist;
+    const u64 S2 = 2 * l * N, So = 2 * (l - 1) * N;
+    auto words_for = [&](std::size_t Bc) {
+        std::size_t w = Bc * (S2 * (nbuf + GG + 2) + So) + 2 * Bc * l * N + ks_words(c, Bc, l) +
+                        rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
+        if (hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
+        return w;
+    };
+    const std::size_t Bc = bsgs_pass_size(c, p, l, words_for);
     Scratch s(c, words_for(Bc));
     std::vector<const u64 *> hp(n), hr(bs);
     for (std::size_t j = 0; j < n; ++j) hp[j] = pdiags[j]->d;
@@ -1245,18 +1315,13 @@ void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t
     const u64 **tabR = reinterpret_cast<const u64 **>(s.take(bs));
     HEC_HIP(hipMemcpyAsync(tabP, hp.data(), n * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
     hec_galois_keys &gkm = const_cast<hec_galois_keys &>(*gk);  // the lazily built per-key tables are caches
-    if (hoist)
-        for (std::size_t nd = 1; nd < trie.nodes.size(); ++nd) {
-            galois_negw(ctx, gkm, trie.nodes[nd].elt);
-            galois_kw(ctx, gkm, trie.nodes[nd].elt, (int)l);
-            if (c.hmac_cfg != 0) galois_mkey(ctx, gkm, trie.nodes[nd].elt);
-        }
+    bsgs_key_tables(ctx, rots, gkm, l);
     const std::size_t mark = s.top;
     const double ql = (double)c.q[l - 1];
     for (std::size_t b0 = 0; b0 < p; b0 += Bc) {
         const std::size_t cnt = std::min(Bc, p - b0);
         s.top = mark;  // every carve of a pass is sized by its own count (the hoisted accumulators are contiguous)
-        TrieBufs bufs(s, per, cnt * S2);
+        TrieBufs bufs(s, rots.per, cnt * S2);
         u64 *A[2] = {s.take(cnt * S2), s.take(cnt * S2)};
         std::vector<u64 *> T(GG);
         for (std::size_t t = 0; t < GG; ++t) T[t] = s.take(cnt * S2);
@@ -1264,31 +1329,7 @@ void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t
         std::vector<Hoist> hs((std::size_t)D);
         if (hoist)
             for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
-        for (std::size_t i = 0; i < cnt; ++i) d2d(c, bufs.b[0][0] + i * S2, cols[b0 + i]->d, S2);
-        const PolyArr Xa{bufs.b[0][0], S2, l * N};
-        auto visit = [&](std::size_t i, PolyArr src) { hr[i] = src.p; };
-        auto keep = [](const u64 *) {};  // no buffer is written twice in a walk
-        auto babies = [&](bool hoisted) {
-            std::fill(bufs.next.begin(), bufs.next.end(), 0u);
-            if (hoisted) {
-                dev_zero(c, c.zflag, 2 * sizeof(int));
-                walk_trie_hoisted(c, s, trie, 0, Xa, 0, (int)cnt, (int)l, ctx, gkm, bufs, hs, S2, c.hoist_min_children,
-                                  visit, keep);
-            } else {
-                walk_trie(c, s, trie, 0, Xa, 0, (int)cnt, (int)l, *gk, bufs, S2, visit, keep);
-            }
-            HEC_HIP(hipMemcpyAsync(tabR, hr.data(), bs * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
-        };
-        babies(hoist);
-        int zfl[2] = {0, 0};
-        if (hoist) HEC_HIP(hipMemcpyAsync(zfl, c.zflag, 2 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-        HEC_HIP(hipStreamSynchronize(c.stream));  // the flag is read; the pointer table has left the host vector
-        if (zfl[0]) {  // a digit limb with more zero coefficients than the hoisted MAC corrects: the babies again
-            if (std::getenv("HEC_DEBUG"))
-                std::fprintf(stderr, "hec: zero-list overflow, baby rotations recomputed without hoisting (p=%zu)\n", cnt);
-            babies(false);
-            HEC_HIP(hipStreamSynchronize(c.stream));
-        }
+        bsgs_babies(ctx, s, rots, gkm, bufs, hs, cols + b0, cnt, l, hr, tabR);
         // inner and giant phases over tiles of GG giants: only one tile of inner sums is live; inner_0 starts the
         // accumulator, every other inner_g is rotated by g bs with the accumulator added in the key switch's last stage
         int cur = 0;
@@ -1309,6 +1350,149 @@ void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t
                 if (g == 0) continue;
                 const PolyArr X{T[t], S2, l * N};
                 const std::vector<u32> &el = gelts[g];
+                for (std::size_t e = 0; e + 1 < el.size(); ++e)
+                    galois_ks(c, s, X, X, (int)cnt, (int)l, el[e], gk->keys.at(el[e]));
+                galois_ks(c, s, X, PolyArr{A[1 - cur], S2, l * N}, (int)cnt, (int)l, el.back(), gk->keys.at(el.back()),
+                          PolyArr{A[cur], S2, l * N});
+                cur = 1 - cur;
+            }
+        }
+        rescale_batch(c, s, PolyArr{A[cur], S2, l * N}, (int)cnt, 2, (int)l, PolyArr{O, So, (l - 1) * N});
+        for (std::size_t i = 0; i < cnt; ++i) store_ct(c, out[b0 + i], O + i * So, 2, l - 1, ps[b0 + i] / ql);
+    }
+    HEC_HIP(hipStreamSynchronize(c.stream));  // the host pointer tables go out of scope
+}
+
+// ---------------------------------------------------------------- baby-step giant-step ct x ct matvec
+// The ct x ct form of the schedule above (opt-in, not the bits of matvec_core unless bs_eff = n):
+//   inner_g = sum_{i < bs, g bs + i < n} multiply(rotate_vector(x, i), A'[g bs + i])         (size 3)
+//   r_g     = relinearize(inner_g)
+//   out     = rescale_to_next(r_0 + sum_{1 <= g < G} rotate_vector(r_g, g bs))
+// with the ciphertext diagonals in BSGS form (A'[j] encrypts diagonal j rotated right by (j / bs) bs slots): the
+// rotations act on size-2 ciphertexts, so every giant group is relinearised before its rotation, (bs - 1) + G +
+// (G - 1) key switches for the n - 1 NAF chains and one relinearisation of the reference loop.
+//
+// The checks, all before anything is written: matvec_check's over the ct x ct operands, the end of the chain, the
+// relinearisation key, rotate_internal's errors over every planned step, the aliasing rule
+std::vector<double> bsgs_ct_check(hec_context *ctx, const hec_ciphertext *const *diags, std::size_t n,
+                                  const BsgsPlan &plan, const hec_ciphertext *const *cols, std::size_t p,
+                                  const hec_kswitch_key *rk, const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    const Ctx &c = ctx->c;
+    need(p >= 1, "empty matrix operand");
+    check_obj(ctx, gk, BAD_GK);
+    for (std::size_t i = 0; i < p; ++i) check_ct(ctx, cols[i]);
+    const std::size_t l = cols[0]->level;
+    for (std::size_t i = 0; i < p; ++i) need(cols[i]->size == 2, "encrypted size must be 2");
+    for (std::size_t i = 0; i < p; ++i) need(cols[i]->level == l, "encrypted1 and encrypted2 parameter mismatch");
+    for (std::size_t j = 0; j < n; ++j) check_ct(ctx, diags[j]);
+    for (std::size_t j = 0; j < n; ++j) need(diags[j]->size == 2, "encrypted size must be 2");
+    for (std::size_t j = 0; j < n; ++j) need(diags[j]->level == l, "encrypted1 and encrypted2 parameter mismatch");
+    std::vector<double> ps(p);
+    for (std::size_t i = 0; i < p; ++i)
+        for (std::size_t j = 0; j < n; ++j) {
+            const double sc = cols[i]->scale * diags[j]->scale;
+            need(scale_ok(c, sc, l), "scale out of bounds");
+            if (j == 0) ps[i] = sc;
+            else need(are_close(ps[i], sc), "scale mismatch");
+        }
+    if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
+    check_obj(ctx, rk, BAD_RK);
+    std::vector<u32> seq;
+    for (int st : plan.steps) {
+        seq.clear();
+        rotation_elts(c, st, *gk, seq);
+    }
+    std::map<const hec_ciphertext *, std::size_t> o;
+    for (std::size_t i = 0; i < p; ++i) {
+        check_obj(ctx, out[i], BAD_CT);
+        need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
+    }
+    for (std::size_t i = 0; i < p; ++i) {
+        const auto it = o.find(cols[i]);
+        need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
+    }
+    for (std::size_t j = 0; j < n; ++j) need(o.find(diags[j]) == o.end(), "an output may alias only its own entry's inputs");
+    return ps;
+}
+
+void bsgs_ct_core(hec_context *ctx, const hec_ciphertext *const *diags, std::size_t n, const BsgsPlan &plan,
+                  const hec_ciphertext *const *cols, std::size_t p, const hec_kswitch_key *rk,
+                  const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    Ctx &c = ctx->c;
+    need(plan.bs <= 512, "bs must be at most 512");  // k_bsgs_inner_ct's exact FP64 sums (hec_kernels.hip)
+    const std::vector<double> ps = bsgs_ct_check(ctx, diags, n, plan, cols, p, rk, gk, out);
+    const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
+    const std::size_t GG = (std::size_t)bsgs_ct_tile(c);
+    const BsgsRots rots = bsgs_rots(c, plan, *gk);
+    const int D = rots.D;
+    const std::size_t nbuf = rots.trie.nodes.size();
+    const u64 S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
+    // a tile's relinearisations run as one key switch over its ng Bc slots while the NTT launches' y-blocks allow
+    const std::size_t ymax = std::max<std::size_t>(1, 65535 / ((l + 1) * l));
+    auto merged = [&](std::size_t Bc) { return GG * Bc <= ymax; };  // by the pass size, so the workspace covers it
+    auto words_for = [&](std::size_t Bc) {
+        const std::size_t Bks = merged(Bc) ? GG * Bc : Bc;
+        std::size_t w = Bc * (S2 * (nbuf + 2) + S3 * GG + So) + 2 * Bc * l * N + ks_words(c, Bks, l) +
+                        rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
+        if (rots.hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
+        return w;
+    };
+    const std::size_t Bc = bsgs_pass_size(c, p, l, words_for);
+    Scratch s(c, words_for(Bc));
+    std::vector<const u64 *> hp(n), hr(bs);
+    for (std::size_t j = 0; j < n; ++j) hp[j] = diags[j]->d;
+    const u64 **tabP = reinterpret_cast<const u64 **>(s.take(n));
+    const u64 **tabR = reinterpret_cast<const u64 **>(s.take(bs));
+    HEC_HIP(hipMemcpyAsync(tabP, hp.data(), n * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
+    hec_galois_keys &gkm = const_cast<hec_galois_keys &>(*gk);  // the lazily built per-key tables are caches
+    bsgs_key_tables(ctx, rots, gkm, l);
+    const std::size_t mark = s.top;
+    const double ql = (double)c.q[l - 1];
+    for (std::size_t b0 = 0; b0 < p; b0 += Bc) {
+        const std::size_t cnt = std::min(Bc, p - b0);
+        s.top = mark;
+        TrieBufs bufs(s, rots.per, cnt * S2);
+        u64 *A[2] = {s.take(cnt * S2), s.take(cnt * S2)};
+        u64 *T = s.take(GG * cnt * S3);  // the tile's size-3 slots, contiguous: slot t at T + t cnt S3
+        u64 *O = s.take(cnt * So);
+        std::vector<Hoist> hs((std::size_t)D);
+        if (rots.hoist)
+            for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
+        bsgs_babies(ctx, s, rots, gkm, bufs, hs, cols + b0, cnt, l, hr, tabR);
+        int cur = 0;
+        for (std::size_t g0 = 0; g0 < G; g0 += GG) {
+            const std::size_t ng = std::min(GG, G - g0);
+            BsgsInner a{};
+            a.R = tabR; a.P = tabP; a.n = n; a.bs = (int)bs; a.g0 = (int)g0; a.ng = (int)ng;
+            for (std::size_t t = 0; t < ng; ++t) a.out[t] = T + t * cnt * S3;
+            {
+                ProfScope pr(c, "bsgs_inner_ct");
+                // the babies once per launch (2 B l each), the tile's diagonals once (2 l each), the outputs once
+                const double nd = (double)(std::min(n, (g0 + ng) * bs) - g0 * bs);
+                ProfScope k(c, "k:k_bsgs_inner_ct", cnt * l * (2.0 * bs + 3.0 * ng) + 2.0 * nd * l);
+                bsgs_inner_ct(c, a, S2, l * N, l * N, S3, l * N, (int)cnt, (int)l);
+            }
+            {  // r_g = relinearize(inner_g), in place in the slot's first two polys; r_0 straight into the accumulator
+                ProfScope pr(c, "bsgs_relin");
+                auto relin = [&](std::size_t t, std::size_t cntk, PolyArr OUT) {
+                    u64 *Tt = T + t * cnt * S3;
+                    keyswitch(c, s, PolyArr{Tt + 2 * l * N, S3, 0}, rk->d, PolyArr{Tt, S3, l * N}, 2, OUT, (int)cntk, (int)l);
+                };
+                std::size_t t = 0;
+                if (g0 == 0) relin(t++, cnt, PolyArr{A[cur], S2, l * N});
+                if (t < ng && merged(Bc)) {
+                    relin(t, (ng - t) * cnt, PolyArr{T + t * cnt * S3, S3, l * N});
+                    t = ng;
+                }
+                for (; t < ng; ++t) relin(t, cnt, PolyArr{T + t * cnt * S3, S3, l * N});
+            }
+            for (std::size_t t = 0; t < ng; ++t) {
+                const std::size_t g = g0 + t;
+                if (g == 0) continue;
+                const PolyArr X{T + t * cnt * S3, S3, l * N};
+                const std::vector<u32> &el = rots.gelts[g];
                 for (std::size_t e = 0; e + 1 < el.size(); ++e)
                     galois_ks(c, s, X, X, (int)cnt, (int)l, el[e], gk->keys.at(el[e]));
                 galois_ks(c, s, X, PolyArr{A[1 - cur], S2, l * N}, (int)cnt, (int)l, el.back(), gk->keys.at(el.back()),
@@ -2043,6 +2227,11 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
                 if (!(value == 2 || value == 4 || (bg ? value == 1 : value == 8 || value == 16)))
                     throw std::invalid_argument("option " + n + (bg ? " takes 1, 2 or 4" : " takes 2, 4, 8 or 16"));
                 (bg ? c.bsgs_bg : c.bsgs_gg) = (int)value;
+            } else if (n == "bsgs_ct_bg" || n == "bsgs_ct_gg") {
+                const bool bg = n == "bsgs_ct_bg";
+                if (!(value == 2 || (bg ? value == 1 : value == 4 || value == 8)))
+                    throw std::invalid_argument("option " + n + (bg ? " takes 1 or 2" : " takes 2, 4 or 8"));
+                (bg ? c.bsgs_ct_bg : c.bsgs_ct_gg) = (int)value;
             } else if (n == "bsgs_order") c.bsgs_order = in(0, 1);
             else throw std::invalid_argument("unknown option");
         };
@@ -3647,6 +3836,17 @@ int hec_matmul_diagpt_col_bsgs(hec_context *ctx, const hec_plaintext *const *pdi
         set_device(ctx);
         need(pdiags && cols && out, "null argument");
         bsgs_core(ctx, pdiags, n, bsgs_plan(n, bs), cols, p, gk, out);
+    });
+}
+
+int hec_matmul_diag_col_bsgs(hec_context *ctx, const hec_ciphertext *const *diags, uint64_t n, uint64_t bs,
+                             const hec_ciphertext *const *cols, uint64_t p, const hec_kswitch_key *rk,
+                             const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    return guard([&] {
+        set_device(ctx);
+        need(diags && cols && out, "null argument");
+        bsgs_ct_core(ctx, diags, n, bsgs_plan(n, bs), cols, p, rk, gk, out);
     });
 }
 

@@ -151,12 +151,14 @@ struct Ctx {
                                    // k_ew_add launch after it.  Same words
     int math_chunk = 0;            // option "math_chunk": ciphertexts per pass of the he::math calls, 0 automatic (the
                                    // 65,535 y-blocks of an NTT launch bound it).  Every value computes the same words
-    int bsgs_chunk = 0;            // option "bsgs_chunk": input vectors per pass of hec_matmul_diagpt_col_bsgs, 0 automatic
+    int bsgs_chunk = 0;            // option "bsgs_chunk": input vectors per pass of the hec_matmul_diag*_col_bsgs calls, 0 automatic
                                    // (the NTT launches' y-blocks and the free device memory bound it).  Same words
     int bsgs_bg = 2, bsgs_gg = 8;  // options "bsgs_bg", "bsgs_gg": k_bsgs_inner's tile, batch entries x giant groups
                                    // per thread (the instantiations of bsgs_inner()).  Same words
     int bsgs_order = 1;            // option "bsgs_order": 1 k_bsgs_inner's batch groups of a coefficient block on
                                    // consecutive block ids, 0 coefficient blocks consecutive.  Same words
+    int bsgs_ct_bg = 2, bsgs_ct_gg = 8;  // options "bsgs_ct_bg", "bsgs_ct_gg": k_bsgs_inner_ct's tile (the instantiations
+                                   // of bsgs_inner_ct()).  Same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -299,6 +301,10 @@ struct BsgsInner {
 };
 int bsgs_tile(const Ctx &c);  // giants per k_bsgs_inner launch (option "bsgs_gg")
 void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int l);
+// the ct x ct form (k_bsgs_inner_ct): P holds the n ciphertext diagonals (size 2, polys a_sk apart), out[t][b] the
+// size-3 sum of the tensor products R[i][b] (x) P[(g0 + t) bs + i], polys o_sk apart; ng <= bsgs_ct_tile(c)
+int bsgs_ct_tile(const Ctx &c);  // giants per k_bsgs_inner_ct launch (option "bsgs_ct_gg")
+void bsgs_inner_ct(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l);
 void tensor_sum(Ctx &c, PolyArr R, PolyArr A, u64 *ACC, u64 acc_sk, int B, int l);
 void ew_add(Ctx &c, PolyArr a, PolyArr b, PolyArr out, int B, int nk, int nl, int mode);  // 0 add, 1 sub
 void ew_negate(Ctx &c, PolyArr a, int B, int nk, int nl);

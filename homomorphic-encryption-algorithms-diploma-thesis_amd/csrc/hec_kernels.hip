@@ -4041,6 +4041,145 @@ void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_
     HEC_HIP(hipGetLastError());
 }
 
+// The inner sums of the baby-step giant-step ct x ct matvec (hec_engine.hip bsgs_ct_core) for a tile of ng <= GG giant
+// groups in one launch: the size-3 tensor products of the baby rotations with the ciphertext diagonals, summed,
+//   OUT_t[b][0] = sum_i R_i[b][0] A'_j[0]
+//   OUT_t[b][1] = sum_i (R_i[b][0] A'_j[1] + R_i[b][1] A'_j[0])
+//   OUT_t[b][2] = sum_i R_i[b][1] A'_j[1]                          j = (g0 + t) bs + i < n,  mod q
+// k_bsgs_inner's shape: a thread owns one coefficient of BG batch entries and the tile's giants, loads per baby the
+// 2 BG rotation words once and each diagonal's two words once for its giants, and keeps 3 BG GG accumulators.  The
+// arithmetic is k_tensor_multi2<PT = false>'s: 60-bit primes reduce d0 and d2 per product (mulmod), form d1 from the
+// 128-bit sum of its two products (mac128, barrett128) and add mod q; FP64 primes sum exact fp_mulmod products as
+// integer-valued doubles and canonicalise once.  Every multiply's words are thus reduced as SEAL reduces them and
+// the sums are exact, so the words equal the per-operation composition's.
+// The FP64 bound: fp_canon takes |x| < 2^52 (hec_device.h).  A product is at most 0.53 q in magnitude, the middle
+// accumulator adds two per term, so |s1| <= 1.06 q bs, and with q < 2^42 (the FP class) that is below 2^52 for
+// bs <= floor(2^10 / 1.06) = 966; s0 and s2 stay at half of that.  The entry therefore refuses bs_eff > 512 (the
+// ct x pt kernel's single product per term allows its 1024).  Every partial sum is an integer below 2^52, so each
+// addition is exact.
+template <int BG, int GG>
+__global__ void __launch_bounds__(256)
+    k_bsgs_inner_ct(BsgsInner a, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int logN, u64 total,
+                    const DevPrime *__restrict__ primes, int nbg, int ncb, int order)
+{
+    const u32 id = blockIdx.x;
+    const int cb = order ? (int)(id / (u32)nbg) : (int)(id % (u32)ncb);
+    const int bgi = order ? (int)(id % (u32)nbg) : (int)(id / (u32)ncb);
+    const u64 idx = (u64)cb * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int b0 = bgi * BG;
+    if (b0 >= B) return;
+    const int nb = min(BG, B - b0);
+    const int ng = min(GG, a.ng);
+    const DevPrime pr = primes[idx >> logN];
+    u64 d0[GG][BG], d1[GG][BG], d2[GG][BG];
+    if (pr.fp) {
+        double s0[GG][BG], s1[GG][BG], s2[GG][BG];
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) s0[t][g] = s1[t][g] = s2[t][g] = 0;
+        for (int i = 0; i < a.bs; ++i) {
+            const u64 *r = a.R[i] + (u64)b0 * r_sb + idx;
+            double r0[BG], r1[BG];
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                const bool on = g < nb;
+                r0[g] = on ? u2d(r[g * r_sb]) : 0.0;
+                r1[g] = on ? u2d(r[g * r_sb + r_sk]) : 0.0;
+            }
+#pragma unroll
+            for (int t = 0; t < GG; ++t) {
+                const u64 j = (u64)(a.g0 + t) * (u64)a.bs + (u64)i;
+                if (t >= ng || j >= a.n) break;  // only the last giant group is partial
+                const u64 *aj = a.P[j] + idx;
+                const double a0 = u2d(aj[0]), a1 = u2d(aj[a_sk]);
+#pragma unroll
+                for (int g = 0; g < BG; ++g) {
+                    s0[t][g] += fp_mulmod(r0[g], a0, pr.qd, pr.qinv);
+                    s1[t][g] += fp_mulmod(r0[g], a1, pr.qd, pr.qinv) + fp_mulmod(r1[g], a0, pr.qd, pr.qinv);
+                    s2[t][g] += fp_mulmod(r1[g], a1, pr.qd, pr.qinv);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                d0[t][g] = fp_canon(s0[t][g], pr.qd, pr.qinv);
+                d1[t][g] = fp_canon(s1[t][g], pr.qd, pr.qinv);
+                d2[t][g] = fp_canon(s2[t][g], pr.qd, pr.qinv);
+            }
+    } else {
+#pragma unroll
+        for (int t = 0; t < GG; ++t)
+#pragma unroll
+            for (int g = 0; g < BG; ++g) d0[t][g] = d1[t][g] = d2[t][g] = 0;
+        for (int i = 0; i < a.bs; ++i) {
+            const u64 *r = a.R[i] + (u64)b0 * r_sb + idx;
+            u64 r0[BG], r1[BG];
+#pragma unroll
+            for (int g = 0; g < BG; ++g) {
+                const bool on = g < nb;
+                r0[g] = on ? r[g * r_sb] : 0;
+                r1[g] = on ? r[g * r_sb + r_sk] : 0;
+            }
+#pragma unroll
+            for (int t = 0; t < GG; ++t) {
+                const u64 j = (u64)(a.g0 + t) * (u64)a.bs + (u64)i;
+                if (t >= ng || j >= a.n) break;
+                const u64 *aj = a.P[j] + idx;
+                const u64 a0 = aj[0], a1 = aj[a_sk];
+#pragma unroll
+                for (int g = 0; g < BG; ++g) {
+                    d0[t][g] = addmod(d0[t][g], mulmod(r0[g], a0, pr), pr.q);
+                    U128 m{r0[g] * a1, mulhi64(r0[g], a1)};
+                    mac128(m, r1[g], a0);
+                    d1[t][g] = addmod(d1[t][g], barrett128(m.lo, m.hi, pr.q, pr.r0, pr.r1), pr.q);
+                    d2[t][g] = addmod(d2[t][g], mulmod(r1[g], a1, pr), pr.q);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < GG; ++t) {
+        if (t >= ng) break;
+        u64 *o = a.out[t] + (u64)b0 * o_sb + idx;
+#pragma unroll
+        for (int g = 0; g < BG; ++g) {
+            if (g >= nb) break;
+            o[g * o_sb] = d0[t][g];
+            o[g * o_sb + o_sk] = d1[t][g];
+            o[g * o_sb + 2 * o_sk] = d2[t][g];
+        }
+    }
+}
+
+int bsgs_ct_tile(const Ctx &c) { return c.bsgs_ct_gg; }
+
+void bsgs_inner_ct(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l)
+{
+    if (a.ng < 1 || a.ng > c.bsgs_ct_gg || a.bs < 1 || a.bs > 512 || B < 1)
+        throw std::logic_error("bsgs_inner_ct: bad tile");
+    const u64 total = (u64)l * c.N;
+    const int BG = c.bsgs_ct_bg, ncb = (int)((total + 255) / 256), nbg = (B + BG - 1) / BG;
+    const dim3 grid((unsigned)((u64)ncb * (u64)nbg));
+#define HEC_BSGS_CT(BGv, GGv)                                                                                      \
+    k_bsgs_inner_ct<BGv, GGv><<<grid, 256, 0, c.stream>>>(a, r_sb, r_sk, a_sk, o_sb, o_sk, B, c.logN, total, c.primes, \
+                                                          nbg, ncb, c.bsgs_order)
+    switch (BG * 32 + c.bsgs_ct_gg) {
+    case 1 * 32 + 2: HEC_BSGS_CT(1, 2); break;
+    case 1 * 32 + 4: HEC_BSGS_CT(1, 4); break;
+    case 1 * 32 + 8: HEC_BSGS_CT(1, 8); break;
+    case 2 * 32 + 2: HEC_BSGS_CT(2, 2); break;
+    case 2 * 32 + 4: HEC_BSGS_CT(2, 4); break;
+    case 2 * 32 + 8: HEC_BSGS_CT(2, 8); break;
+    default: throw std::logic_error("bsgs_inner_ct: no kernel for this tile");
+    }
+#undef HEC_BSGS_CT
+    HEC_HIP(hipGetLastError());
+}
+
 // ACC (size 3) = sum_b R[b] (x) A[b]  (col x col^T form: one output, the batch is the j-sum)
 __global__ void __launch_bounds__(256)
     k_tensor_sum(PolyArr R, PolyArr A, u64 *__restrict__ ACC, u64 acc_sk, int B, int logN, u64 total,

@@ -316,6 +316,34 @@ int hec_bsgs_plan(uint64_t n, uint64_t bs, int *steps, uint64_t cap, uint64_t *c
 int hec_matmul_diagpt_col_bsgs(hec_context *ctx, const hec_plaintext *const *pdiags, uint64_t n, uint64_t bs,
                                const hec_ciphertext *const *cols, uint64_t p, const hec_galois_keys *gk,
                                hec_ciphertext *const *out);
+/* ct x ct matvec on the baby-step giant-step schedule: the product of hec_matmul_diag_col (BatchedMatrix::matmul
+ * diag x col, he_linalg.cpp:943-1006) from (bs_eff - 1) baby rotations, G relinearisations and (G - 1) giant
+ * rotations, G = ceil(n / bs_eff), bs_eff = min(bs, n), bs = 0 hec_bsgs_plan's choice:
+ *   inner_g = sum_{i < bs_eff, g bs_eff + i < n} multiply(rotate_vector(cols[c], i), diags[g bs_eff + i])   (size 3)
+ *   r_g     = relinearize(inner_g, rk)
+ *   out[c]  = rescale_to_next( r_0 + sum_{1 <= g < G} rotate_vector(r_g, g bs_eff) )
+ * diags are in BSGS form: diags[j] encrypts diagonal j's slot vector rotated right by (j / bs_eff) bs_eff slots (the
+ * client rolls the slot vector before encrypting it, which costs nothing and adds no noise).  The rotation steps are
+ * those of hec_bsgs_plan.  NOT bit-identical to hec_matmul_diag_col unless bs_eff = n, where G = 1 and the two
+ * definitions coincide (it decrypts to the same product; every giant group's relinearisation adds its own noise); it
+ * IS word for word, with level and scale, what the per-operation calls above give when composed in this order,
+ * rotate_vector by SEAL's rule (the step's own key, else its NAF chain).
+ * bs_eff > 512 is HEC_EINVAL "bs must be at most 512": the inner-sum kernel adds two exact FP64 products per term,
+ * which stays below 2^52 for 966 terms at most; the ct x pt call keeps its 1024.
+ * Every check comes before the first write, in this order: objects and the Galois keys of this context, sizes 2,
+ * one level, "scale out of bounds" and "scale mismatch" over every product, "end of modulus switching chain
+ * reached", rk of this context, "Galois key not present" over every step of hec_bsgs_plan, the aliasing rule: out[c]
+ * may be cols[c]; an output that is another entry's input or a diagonal, or listed twice, is HEC_EINVAL.
+ * A pass of Bc input vectors holds (nodes + 2 + 1.5 GG) Bc ciphertexts of workspace beside the key switch's own,
+ * which covers GG Bc entries when the tile's relinearisations run as one key switch (GG Bc (l + 1) l <= 65,535):
+ * nodes = the nodes of the baby rotations' prefix trie (as for hec_matmul_diagpt_col_bsgs), GG = "bsgs_ct_gg" size-3
+ * slots.  Bc is halved until that fits the free device memory; when not even one vector fits, the call fails with
+ * HEC_EDEVICE.  Runs on the context's stream in passes of at most "bsgs_chunk" input vectors; the outputs do not
+ * depend on it, nor on "bsgs_ct_bg" (1, 2), "bsgs_ct_gg" (2, 4, 8) and "bsgs_order" (0..1), the inner-sum kernel's
+ * tile and grid order.  Batch lanes and the sharded path do not take this route. */
+int hec_matmul_diag_col_bsgs(hec_context *ctx, const hec_ciphertext *const *diags, uint64_t n, uint64_t bs,
+                             const hec_ciphertext *const *cols, uint64_t p, const hec_kswitch_key *rk,
+                             const hec_galois_keys *gk, hec_ciphertext *const *out);
 /* relinearize + rescale a batch of size-3 accumulators (he_linalg.cpp:999-1002) */
 int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, const hec_kswitch_key *rk,
                       hec_ciphertext *const *out);

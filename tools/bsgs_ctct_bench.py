@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""The baby-step giant-step ct x ct matvec (hec_matmul_diag_col_bsgs) against the reference schedule
+(hec_matmul_diag_col) at cfg3: N = 2^15, {60, 40 x 9, 60}, level 10, n = 4096, scale 2^40, on uniform synthetic
+ciphertexts and keys.  Sides, all in one process, alternated, timed with HIP events on the context's stream after a
+warm-up of every side:
+  bsgs32 / bsgs64 / bsgs128 / bsgs256   bs = 32, 64, 128, 256 with a Galois key for every planned step
+  bsgs64_default                        bs = 64 on the default (power-of-two) key set: NAF chains
+  reference                             hec_matmul_diag_col on the default key set
+The sides do not share their ciphertext bits (tests/test_gpu_bsgs_ctct.py checks each against the oracle), so nothing
+is compared here but the tile variants of k_bsgs_inner_ct with the default tile, word for word on three outputs.
+Prints one JSON line: matvec/s per side (median of the repetitions, spread = (max - min) / median), the key switches
+per input vector from the plans (rotations + relinearisations), the per-class table of bs = 64 from a separate
+profiled run (each kernel class's ms, GB/s on its algorithmic bytes and share of the call), and k_bsgs_inner_ct's time
+per tile (options "bsgs_ct_bg", "bsgs_ct_gg", "bsgs_order") from profiled runs of their own.
+
+    python tools/bsgs_ctct_bench.py [--b 128] [--n 4096] [--reps 3] [--out profiles/bsgs_ctct_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+N, BITS, SCALE = 1 << 15, [60] + [40] * 9 + [60], 2.0**40
+BLOCK_SIZES = (32, 64, 128, 256)
+TILES = [(2, 8, 1), (2, 8, 0), (2, 4, 1), (2, 2, 1), (1, 2, 1), (1, 4, 1), (1, 8, 1)]  # (bg, gg, order); first = default
+OPTS = ("bsgs_ct_bg", "bsgs_ct_gg", "bsgs_order")
+
+
+def default_key_switches(n, bs):
+    """Rotation key switches per input vector on the default key set: the distinct prefixes of the babies' NAF chains
+    (the rotation trie) and every element of the giants' chains."""
+    from _helpers import rotation_seq
+    pre = set()
+    for i in range(1, min(bs, n)):
+        s = tuple(rotation_seq(N, i))
+        pre |= {s[:k] for k in range(1, len(s) + 1)}
+    eff = min(bs, n)
+    return len(pre) + sum(len(rotation_seq(N, g * eff)) for g in range(1, -(-n // eff)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--b", type=int, default=128, help="input vectors per call")
+    ap.add_argument("--n", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=3, help="timed runs of each side, alternated (at least 3)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    reps, B, n = max(3, args.reps), args.b, args.n
+
+    import torch
+    if not torch.cuda.is_available():  # one HIP runtime for torch and the engine; no device, no measurement
+        print("bsgs_ctct_bench: no GPU", file=sys.stderr)
+        return 1
+    from _helpers import load_hecdna, rotation_trie_stats
+    hec = load_hecdna()
+    ctx = hec.Context(N, hec.create_coeff_modulus(N, BITS))
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    L = len(BITS) - 1
+    diags = [hec.Ciphertext(ctx).fill_uniform(2, L, SCALE, 20000 + j) for j in range(n)]
+    xs = [hec.Ciphertext(ctx).fill_uniform(2, L, SCALE, 1000 + i) for i in range(B)]
+    steps = sorted({s for bs in BLOCK_SIZES for s in hec.bsgs_plan(n, bs)[1]})
+    gk_steps = ctx.galois_keys(uniform_elts=[ctx.elt_from_step(s) for s in steps], seed=77)  # a key per step of all
+    gk_def = ctx.galois_keys(uniform_elts=ctx.default_galois_elts(), seed=78)
+    rk = ctx.relin_key(seed=79)
+    outs = {}  # every side writes into its own outputs: no allocation in the timed calls
+
+    def side(name, fn):
+        outs[name] = [hec.Ciphertext(ctx) for _ in range(B)]
+        return lambda: fn(outs[name])
+
+    sides = {f"bsgs{bs}": side(f"bsgs{bs}", lambda o, bs=bs: ctx.matmul_diag_col_bsgs(diags, xs, rk, gk_steps, bs=bs, out=o))
+             for bs in BLOCK_SIZES}
+    sides["bsgs64_default"] = side("bsgs64_default",
+                                   lambda o: ctx.matmul_diag_col_bsgs(diags, xs, rk, gk_def, bs=64, out=o))
+    sides["reference"] = side("reference", lambda o: ctx.matmul_diag_col(diags, xs, rk, gk_def, out=o))
+    groups = lambda bs: -(-n // min(bs, n))  # noqa: E731
+    ks = {f"bsgs{bs}": len(hec.bsgs_plan(n, bs)[1]) + groups(bs) for bs in BLOCK_SIZES}
+    ks["bsgs64_default"] = default_key_switches(n, 64) + groups(64)
+    ks["reference"] = rotation_trie_stats(N, n)[0] + 1
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ctx.synchronize()
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    for k, fn in sides.items():  # warm-up of every side: workspace, output buffers, per-key tables
+        fn()
+        ctx.synchronize()
+        print(f"bsgs_ctct_bench: warmed {k}", file=sys.stderr, flush=True)
+    times = {k: [] for k in sides}
+    for _ in range(reps):  # alternated
+        for k, fn in sides.items():
+            times[k].append(timed(fn))
+            print(f"bsgs_ctct_bench: {k} {times[k][-1]:.1f} ms", file=sys.stderr, flush=True)
+    result = {"N": N, "moduli_bits": BITS, "level": L, "n": n, "B": B, "reps": reps, "sides": {}}
+    for k, ms in times.items():
+        med = float(np.median(ms))
+        result["sides"][k] = {"ms": round(med, 2), "matvec_per_s": round(B / (med * 1e-3), 2),
+                              "spread": round((max(ms) - min(ms)) / med, 4), "runs_ms": [round(v, 2) for v in ms],
+                              "key_switches": ks[k]}
+    ref = result["sides"]["reference"]["matvec_per_s"]
+    for k in sides:
+        result["sides"][k]["over_reference"] = round(result["sides"][k]["matvec_per_s"] / ref, 2)
+
+    def profiled(fn):
+        """A run of its own under the asynchronous profile: (call ms, {class: (ms, scopes, bytes, launches)})."""
+        ctx.profile(2)
+        ms = timed(fn)
+        tab = {cls: ctx.profile_read_ex(cls) for cls in ctx.profile_classes()}
+        ctx.profile(0)
+        return ms, tab
+
+    call_ms, tab = profiled(sides["bsgs64"])
+    result["bsgs64_classes"] = {"call_ms": round(call_ms, 2), "kernels": {
+        cls: {"ms": round(ms, 3), "launches": kl, "share": round(ms / call_ms, 4),
+              "GBps": round(nb / (ms * 1e-3) / 1e9, 1) if ms and nb else None}
+        for cls, (ms, _scopes, nb, kl) in sorted(tab.items()) if cls.startswith("k:")},
+        "scopes": {cls: round(tab[cls][0], 3) for cls in ("bsgs_inner_ct", "bsgs_relin") if cls in tab}}
+
+    # k_bsgs_inner_ct per tile at bs = 64, and the outputs of every tile against the default tile's
+    want = [outs["bsgs64"][i].download() for i in (0, B // 2, B - 1)]
+    result["tiles"], equal = [], True
+    for tile in TILES:
+        for k, v in zip(OPTS, tile):
+            ctx.set_option(k, v)
+        sides["bsgs64"]()  # warm-up: the tile changes the workspace
+        runs = []
+        for _ in range(reps):
+            ms_call, t = profiled(sides["bsgs64"])
+            ms, _scopes, nb, kl = t["k:k_bsgs_inner_ct"]
+            runs.append((ms, nb, kl, ms_call))
+        ms, nb, kl, ms_call = sorted(runs)[len(runs) // 2]
+        equal = equal and all(np.array_equal(outs["bsgs64"][i].download(), w) for i, w in zip((0, B // 2, B - 1), want))
+        print(f"bsgs_ctct_bench: tile {tile}: k_bsgs_inner_ct {ms:.2f} ms", file=sys.stderr, flush=True)
+        result["tiles"].append({"bg": tile[0], "gg": tile[1], "order": tile[2], "k_bsgs_inner_ct_ms": round(ms, 3),
+                                "launches": kl, "GBps": round(nb / (ms * 1e-3) / 1e9, 1), "call_ms": round(ms_call, 2),
+                                "spread": round((max(r[0] for r in runs) - min(r[0] for r in runs)) / ms, 4)})
+    for k, v in zip(OPTS, TILES[0]):
+        ctx.set_option(k, v)
+    result["tiles_equal"] = bool(equal)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if equal else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
