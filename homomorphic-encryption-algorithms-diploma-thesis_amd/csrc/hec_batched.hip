@@ -662,18 +662,6 @@ static std::map<std::size_t, std::vector<std::size_t>> by_level(const hec_cipher
     return g;
 }
 };
-// an output written by one pass must not be an input that a later pass gathers
-void check_out_alias(const std::vector<const hec_ciphertext *const *> &ins, hec_ciphertext *const *out, uint64_t B)
-{
-    std::map<const hec_ciphertext *, uint64_t> o;
-    for (uint64_t i = 0; i < B; ++i)
-        need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
-    for (const hec_ciphertext *const *in : ins)
-        for (uint64_t i = 0; i < B; ++i) {
-            const auto it = o.find(in[i]);
-            need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
-        }
-}
 
 // The schedule of BatchedVector::sum_elems_inplace (he_linalg.cpp:667-713), written once over three operations on
 // slots of one Scratch workspace: rot, add and drop.  As MathRun, a call walks it twice: first without a device side

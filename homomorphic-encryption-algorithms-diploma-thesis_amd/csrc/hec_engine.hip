@@ -633,6 +633,22 @@ void check_ct(const hec_context *ctx, const hec_ciphertext *a)
     check_obj(ctx, a, BAD_CT);
     need(a->level >= 1 && a->level <= ctx->c.L && a->size >= 2 && a->d, BAD_CT);
 }
+void check_out_alias(const std::vector<const hec_ciphertext *const *> &ins, hec_ciphertext *const *out, uint64_t B,
+                     const hec_context *ctx, const hec_ciphertext *const *never, uint64_t n_never)
+{
+    constexpr const char *msg = "an output may alias only its own entry's inputs";
+    std::map<const hec_ciphertext *, uint64_t> o;
+    for (uint64_t i = 0; i < B; ++i) {
+        if (ctx) check_obj(ctx, out[i], BAD_CT);
+        need(o.emplace(out[i], i).second, msg);
+    }
+    for (const hec_ciphertext *const *in : ins)
+        for (uint64_t i = 0; i < B; ++i) {
+            const auto it = o.find(in[i]);
+            need(it == o.end() || it->second == i, msg);
+        }
+    for (uint64_t j = 0; j < n_never; ++j) need(o.find(never[j]) == o.end(), msg);
+}
 }  // namespace hec
 namespace {
 void check_plain_data(const hec_context *ctx, const hec_plaintext *p)  // holds data; the caller compares the level
@@ -1126,8 +1142,9 @@ void matvec_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec
     for (std::size_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, ps[i] / ql);
 }
 
-// ---------------------------------------------------------------- baby-step giant-step ct x pt matvec
-// The same product over another schedule (opt-in, not the bits of matvec_core unless bs_eff = n):
+// ---------------------------------------------------------------- baby-step giant-step matvec, ct x pt and ct x ct
+// The same product over another schedule (opt-in, not the bits of matvec_core unless bs_eff = n).  The
+// ct x pt form (the ct x ct form's own steps are at bsgs_core):
 //   inner_g = sum_{i < bs, g bs + i < n} multiply_plain(rotate_vector(x, i), P'[g bs + i])
 //   out     = rescale_to_next(inner_0 + sum_{1 <= g < G} rotate_vector(inner_g, g bs))
 // with the plaintext diagonals in BSGS form (P'[j] encodes diagonal j rotated right by (j / bs) bs slots), so
@@ -1154,45 +1171,46 @@ BsgsPlan bsgs_plan(uint64_t n, uint64_t bs)
 }
 
 // matvec_check's checks in its order over the BSGS schedule's operations, all before anything is written; returns the
-// product scale of every output
-std::vector<double> bsgs_check(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
-                               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk,
-                               hec_ciphertext *const *out)
+// product scale of every output.  diags or pdiags, as matvec_check.  The aliasing rule (out[i] may be
+// cols[i]; no diagonal may be an output) keeps each form's place: before the scale checks for ct x pt, last for ct x ct
+std::vector<double> bsgs_check(hec_context *ctx, const hec_ciphertext *const *diags, const hec_plaintext *const *pdiags,
+                               std::size_t n, const BsgsPlan &plan, const hec_ciphertext *const *cols, std::size_t p,
+                               const hec_kswitch_key *rk, const hec_galois_keys *gk, hec_ciphertext *const *out)
 {
     const Ctx &c = ctx->c;
+    const bool pt = pdiags != nullptr;
     need(p >= 1, "empty matrix operand");
     check_obj(ctx, gk, BAD_GK);
     for (std::size_t i = 0; i < p; ++i) check_ct(ctx, cols[i]);
     const std::size_t l = cols[0]->level;
     for (std::size_t i = 0; i < p; ++i) need(cols[i]->size == 2, "encrypted size must be 2");
     for (std::size_t i = 0; i < p; ++i) need(cols[i]->level == l, "encrypted1 and encrypted2 parameter mismatch");
-    for (std::size_t j = 0; j < n; ++j) check_plain_data(ctx, pdiags[j]);
-    for (std::size_t j = 0; j < n; ++j) need(pdiags[j]->level == l, "encrypted_ntt and plain_ntt parameter mismatch");
-    {  // out[i] may be cols[i]; an output that is another entry's input, or listed twice, is refused
-        std::map<const hec_ciphertext *, std::size_t> o;
-        for (std::size_t i = 0; i < p; ++i) {
-            check_obj(ctx, out[i], BAD_CT);
-            need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
-        }
-        for (std::size_t i = 0; i < p; ++i) {
-            const auto it = o.find(cols[i]);
-            need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
-        }
+    if (pt) {
+        for (std::size_t j = 0; j < n; ++j) check_plain_data(ctx, pdiags[j]);
+        for (std::size_t j = 0; j < n; ++j)
+            need(pdiags[j]->level == l, "encrypted_ntt and plain_ntt parameter mismatch");
+        check_out_alias({cols}, out, p, ctx);
+    } else {
+        for (std::size_t j = 0; j < n; ++j) check_ct(ctx, diags[j]);
+        for (std::size_t j = 0; j < n; ++j) need(diags[j]->size == 2, "encrypted size must be 2");
+        for (std::size_t j = 0; j < n; ++j) need(diags[j]->level == l, "encrypted1 and encrypted2 parameter mismatch");
     }
     std::vector<double> ps(p);
     for (std::size_t i = 0; i < p; ++i)
         for (std::size_t j = 0; j < n; ++j) {
-            const double sc = cols[i]->scale * pdiags[j]->scale;
+            const double sc = cols[i]->scale * (pt ? pdiags[j]->scale : diags[j]->scale);
             need(scale_ok(c, sc, l), "scale out of bounds");
             if (j == 0) ps[i] = sc;
             else need(are_close(ps[i], sc), "scale mismatch");
         }
     if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
+    if (!pt) check_obj(ctx, rk, BAD_RK);
     std::vector<u32> seq;  // rotate_internal's own errors over every planned step
     for (int st : plan.steps) {
         seq.clear();
         rotation_elts(c, st, *gk, seq);
     }
+    if (!pt) check_out_alias({cols}, out, p, ctx, diags, n);
     return ps;
 }
 
@@ -1288,29 +1306,47 @@ void bsgs_babies(hec_context *ctx, Scratch &s, const BsgsRots &r, hec_galois_key
     }
 }
 
-void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t n, const BsgsPlan &plan,
-               const hec_ciphertext *const *cols, std::size_t p, const hec_galois_keys *gk, hec_ciphertext *const *out)
+// The ct x ct form of the schedule multiplies by ciphertext diagonals, so its inner sums have size 3:
+//   inner_g = sum_{i < bs, g bs + i < n} multiply(rotate_vector(x, i), A'[g bs + i])         (size 3)
+//   r_g     = relinearize(inner_g)
+//   out     = rescale_to_next(r_0 + sum_{1 <= g < G} rotate_vector(r_g, g bs))
+// with the ciphertext diagonals in BSGS form (A'[j] encrypts diagonal j rotated right by (j / bs) bs slots): the
+// rotations act on size-2 ciphertexts, so every giant group is relinearised before its rotation, (bs - 1) + G +
+// (G - 1) key switches for the n - 1 NAF chains and one relinearisation of the reference loop.
+//
+// One core for both forms: diags (ct x ct, with rk) or pdiags (ct x pt, rk unused), exactly one non-null, as
+// matvec_core.  The forms differ in the inner-sum kernel and its slot stride (size 3 or 2), in the relinearisation
+// between the inner and the giant phase, and in where inner_0 lands (ct x pt: straight into the accumulator)
+void bsgs_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec_plaintext *const *pdiags, std::size_t n,
+               const BsgsPlan &plan, const hec_ciphertext *const *cols, std::size_t p, const hec_kswitch_key *rk,
+               const hec_galois_keys *gk, hec_ciphertext *const *out)
 {
     Ctx &c = ctx->c;
-    const std::vector<double> ps = bsgs_check(ctx, pdiags, n, plan, cols, p, gk, out);
+    const bool pt = pdiags != nullptr;
+    if (!pt) need(plan.bs <= 512, "bs must be at most 512");  // k_bsgs_inner_ct's exact FP64 sums (hec_kernels.hip)
+    const std::vector<double> ps = bsgs_check(ctx, diags, pdiags, n, plan, cols, p, rk, gk, out);
     const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
-    const std::size_t GG = (std::size_t)bsgs_tile(c);
+    const std::size_t GG = (std::size_t)bsgs_tile(c, !pt);
     const BsgsRots rots = bsgs_rots(c, plan, *gk);
-    const std::vector<std::vector<u32>> &gelts = rots.gelts;
     const int D = rots.D;
     const std::size_t nbuf = rots.trie.nodes.size();
-    const bool hoist = rots.hoist;
-    const u64 S2 = 2 * l * N, So = 2 * (l - 1) * N;
+    const u64 S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
+    const u64 Sin = pt ? S2 : S3;  // an inner sum's stride
+    // ct x ct: a tile's relinearisations run as one key switch over its ng Bc slots while the NTT launches' y-blocks
+    // allow
+    const std::size_t ymax = std::max<std::size_t>(1, 65535 / ((l + 1) * l));
+    auto merged = [&](std::size_t Bc) { return !pt && GG * Bc <= ymax; };  // by the pass size: the workspace covers it
     auto words_for = [&](std::size_t Bc) {
-        std::size_t w = Bc * (S2 * (nbuf + GG + 2) + So) + 2 * Bc * l * N + ks_words(c, Bc, l) +
+        const std::size_t Bks = merged(Bc) ? GG * Bc : Bc;
+        std::size_t w = Bc * (S2 * (nbuf + 2) + Sin * GG + So) + 2 * Bc * l * N + ks_words(c, Bks, l) +
                         rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
-        if (hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
+        if (rots.hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
         return w;
     };
     const std::size_t Bc = bsgs_pass_size(c, p, l, words_for);
     Scratch s(c, words_for(Bc));
     std::vector<const u64 *> hp(n), hr(bs);
-    for (std::size_t j = 0; j < n; ++j) hp[j] = pdiags[j]->d;
+    for (std::size_t j = 0; j < n; ++j) hp[j] = pt ? pdiags[j]->d : diags[j]->d;
     const u64 **tabP = reinterpret_cast<const u64 **>(s.take(n));
     const u64 **tabR = reinterpret_cast<const u64 **>(s.take(bs));
     HEC_HIP(hipMemcpyAsync(tabP, hp.data(), n * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
@@ -1323,175 +1359,50 @@ void bsgs_core(hec_context *ctx, const hec_plaintext *const *pdiags, std::size_t
         s.top = mark;  // every carve of a pass is sized by its own count (the hoisted accumulators are contiguous)
         TrieBufs bufs(s, rots.per, cnt * S2);
         u64 *A[2] = {s.take(cnt * S2), s.take(cnt * S2)};
-        std::vector<u64 *> T(GG);
-        for (std::size_t t = 0; t < GG; ++t) T[t] = s.take(cnt * S2);
-        u64 *O = s.take(cnt * So);
-        std::vector<Hoist> hs((std::size_t)D);
-        if (hoist)
-            for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
-        bsgs_babies(ctx, s, rots, gkm, bufs, hs, cols + b0, cnt, l, hr, tabR);
-        // inner and giant phases over tiles of GG giants: only one tile of inner sums is live; inner_0 starts the
-        // accumulator, every other inner_g is rotated by g bs with the accumulator added in the key switch's last stage
-        int cur = 0;
-        for (std::size_t g0 = 0; g0 < G; g0 += GG) {
-            const std::size_t ng = std::min(GG, G - g0);
-            BsgsInner a{};
-            a.R = tabR; a.P = tabP; a.n = n; a.bs = (int)bs; a.g0 = (int)g0; a.ng = (int)ng;
-            for (std::size_t t = 0; t < ng; ++t) a.out[t] = g0 + t == 0 ? A[cur] : T[t];
-            {
-                ProfScope pr(c, "bsgs_inner");
-                // the babies once per launch (2 B l each), the tile's plaintexts once (l each), the outputs once
-                const double npt = (double)(std::min(n, (g0 + ng) * bs) - g0 * bs);
-                ProfScope k(c, "k:k_bsgs_inner", 2.0 * cnt * l * (double)(bs + ng) + npt * l);
-                bsgs_inner(c, a, S2, l * N, S2, l * N, (int)cnt, (int)l);
-            }
-            for (std::size_t t = 0; t < ng; ++t) {
-                const std::size_t g = g0 + t;
-                if (g == 0) continue;
-                const PolyArr X{T[t], S2, l * N};
-                const std::vector<u32> &el = gelts[g];
-                for (std::size_t e = 0; e + 1 < el.size(); ++e)
-                    galois_ks(c, s, X, X, (int)cnt, (int)l, el[e], gk->keys.at(el[e]));
-                galois_ks(c, s, X, PolyArr{A[1 - cur], S2, l * N}, (int)cnt, (int)l, el.back(), gk->keys.at(el.back()),
-                          PolyArr{A[cur], S2, l * N});
-                cur = 1 - cur;
-            }
-        }
-        rescale_batch(c, s, PolyArr{A[cur], S2, l * N}, (int)cnt, 2, (int)l, PolyArr{O, So, (l - 1) * N});
-        for (std::size_t i = 0; i < cnt; ++i) store_ct(c, out[b0 + i], O + i * So, 2, l - 1, ps[b0 + i] / ql);
-    }
-    HEC_HIP(hipStreamSynchronize(c.stream));  // the host pointer tables go out of scope
-}
-
-// ---------------------------------------------------------------- baby-step giant-step ct x ct matvec
-// The ct x ct form of the schedule above (opt-in, not the bits of matvec_core unless bs_eff = n):
-//   inner_g = sum_{i < bs, g bs + i < n} multiply(rotate_vector(x, i), A'[g bs + i])         (size 3)
-//   r_g     = relinearize(inner_g)
-//   out     = rescale_to_next(r_0 + sum_{1 <= g < G} rotate_vector(r_g, g bs))
-// with the ciphertext diagonals in BSGS form (A'[j] encrypts diagonal j rotated right by (j / bs) bs slots): the
-// rotations act on size-2 ciphertexts, so every giant group is relinearised before its rotation, (bs - 1) + G +
-// (G - 1) key switches for the n - 1 NAF chains and one relinearisation of the reference loop.
-//
-// The checks, all before anything is written: matvec_check's over the ct x ct operands, the end of the chain, the
-// relinearisation key, rotate_internal's errors over every planned step, the aliasing rule
-std::vector<double> bsgs_ct_check(hec_context *ctx, const hec_ciphertext *const *diags, std::size_t n,
-                                  const BsgsPlan &plan, const hec_ciphertext *const *cols, std::size_t p,
-                                  const hec_kswitch_key *rk, const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    const Ctx &c = ctx->c;
-    need(p >= 1, "empty matrix operand");
-    check_obj(ctx, gk, BAD_GK);
-    for (std::size_t i = 0; i < p; ++i) check_ct(ctx, cols[i]);
-    const std::size_t l = cols[0]->level;
-    for (std::size_t i = 0; i < p; ++i) need(cols[i]->size == 2, "encrypted size must be 2");
-    for (std::size_t i = 0; i < p; ++i) need(cols[i]->level == l, "encrypted1 and encrypted2 parameter mismatch");
-    for (std::size_t j = 0; j < n; ++j) check_ct(ctx, diags[j]);
-    for (std::size_t j = 0; j < n; ++j) need(diags[j]->size == 2, "encrypted size must be 2");
-    for (std::size_t j = 0; j < n; ++j) need(diags[j]->level == l, "encrypted1 and encrypted2 parameter mismatch");
-    std::vector<double> ps(p);
-    for (std::size_t i = 0; i < p; ++i)
-        for (std::size_t j = 0; j < n; ++j) {
-            const double sc = cols[i]->scale * diags[j]->scale;
-            need(scale_ok(c, sc, l), "scale out of bounds");
-            if (j == 0) ps[i] = sc;
-            else need(are_close(ps[i], sc), "scale mismatch");
-        }
-    if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
-    check_obj(ctx, rk, BAD_RK);
-    std::vector<u32> seq;
-    for (int st : plan.steps) {
-        seq.clear();
-        rotation_elts(c, st, *gk, seq);
-    }
-    std::map<const hec_ciphertext *, std::size_t> o;
-    for (std::size_t i = 0; i < p; ++i) {
-        check_obj(ctx, out[i], BAD_CT);
-        need(o.emplace(out[i], i).second, "an output may alias only its own entry's inputs");
-    }
-    for (std::size_t i = 0; i < p; ++i) {
-        const auto it = o.find(cols[i]);
-        need(it == o.end() || it->second == i, "an output may alias only its own entry's inputs");
-    }
-    for (std::size_t j = 0; j < n; ++j) need(o.find(diags[j]) == o.end(), "an output may alias only its own entry's inputs");
-    return ps;
-}
-
-void bsgs_ct_core(hec_context *ctx, const hec_ciphertext *const *diags, std::size_t n, const BsgsPlan &plan,
-                  const hec_ciphertext *const *cols, std::size_t p, const hec_kswitch_key *rk,
-                  const hec_galois_keys *gk, hec_ciphertext *const *out)
-{
-    Ctx &c = ctx->c;
-    need(plan.bs <= 512, "bs must be at most 512");  // k_bsgs_inner_ct's exact FP64 sums (hec_kernels.hip)
-    const std::vector<double> ps = bsgs_ct_check(ctx, diags, n, plan, cols, p, rk, gk, out);
-    const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
-    const std::size_t GG = (std::size_t)bsgs_ct_tile(c);
-    const BsgsRots rots = bsgs_rots(c, plan, *gk);
-    const int D = rots.D;
-    const std::size_t nbuf = rots.trie.nodes.size();
-    const u64 S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
-    // a tile's relinearisations run as one key switch over its ng Bc slots while the NTT launches' y-blocks allow
-    const std::size_t ymax = std::max<std::size_t>(1, 65535 / ((l + 1) * l));
-    auto merged = [&](std::size_t Bc) { return GG * Bc <= ymax; };  // by the pass size, so the workspace covers it
-    auto words_for = [&](std::size_t Bc) {
-        const std::size_t Bks = merged(Bc) ? GG * Bc : Bc;
-        std::size_t w = Bc * (S2 * (nbuf + 2) + S3 * GG + So) + 2 * Bc * l * N + ks_words(c, Bks, l) +
-                        rescale_words(c, Bc, 2, l) + bs + n + (nbuf + GG + 100) * 64;
-        if (rots.hoist) w += (std::size_t)D * hoist_words(c, Bc, l) + hoisted_child_words(c, Bc, l);
-        return w;
-    };
-    const std::size_t Bc = bsgs_pass_size(c, p, l, words_for);
-    Scratch s(c, words_for(Bc));
-    std::vector<const u64 *> hp(n), hr(bs);
-    for (std::size_t j = 0; j < n; ++j) hp[j] = diags[j]->d;
-    const u64 **tabP = reinterpret_cast<const u64 **>(s.take(n));
-    const u64 **tabR = reinterpret_cast<const u64 **>(s.take(bs));
-    HEC_HIP(hipMemcpyAsync(tabP, hp.data(), n * sizeof(u64 *), hipMemcpyHostToDevice, c.stream));
-    hec_galois_keys &gkm = const_cast<hec_galois_keys &>(*gk);  // the lazily built per-key tables are caches
-    bsgs_key_tables(ctx, rots, gkm, l);
-    const std::size_t mark = s.top;
-    const double ql = (double)c.q[l - 1];
-    for (std::size_t b0 = 0; b0 < p; b0 += Bc) {
-        const std::size_t cnt = std::min(Bc, p - b0);
-        s.top = mark;
-        TrieBufs bufs(s, rots.per, cnt * S2);
-        u64 *A[2] = {s.take(cnt * S2), s.take(cnt * S2)};
-        u64 *T = s.take(GG * cnt * S3);  // the tile's size-3 slots, contiguous: slot t at T + t cnt S3
+        u64 *T = s.take(GG * cnt * Sin);  // the tile's inner sums, contiguous: slot t at T + t cnt Sin
+        auto slot = [&](std::size_t t) { return T + t * cnt * Sin; };
         u64 *O = s.take(cnt * So);
         std::vector<Hoist> hs((std::size_t)D);
         if (rots.hoist)
             for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
         bsgs_babies(ctx, s, rots, gkm, bufs, hs, cols + b0, cnt, l, hr, tabR);
+        // inner and giant phases over tiles of GG giants: only one tile of inner sums is live; inner_0 (ct x ct: r_0)
+        // starts the accumulator, every other one is rotated by g bs with the accumulator added in the key switch's
+        // last stage
         int cur = 0;
         for (std::size_t g0 = 0; g0 < G; g0 += GG) {
             const std::size_t ng = std::min(GG, G - g0);
             BsgsInner a{};
             a.R = tabR; a.P = tabP; a.n = n; a.bs = (int)bs; a.g0 = (int)g0; a.ng = (int)ng;
-            for (std::size_t t = 0; t < ng; ++t) a.out[t] = T + t * cnt * S3;
+            for (std::size_t t = 0; t < ng; ++t) a.out[t] = pt && g0 + t == 0 ? A[cur] : slot(t);
             {
-                ProfScope pr(c, "bsgs_inner_ct");
-                // the babies once per launch (2 B l each), the tile's diagonals once (2 l each), the outputs once
+                ProfScope pr(c, pt ? "bsgs_inner" : "bsgs_inner_ct");
+                // the babies once per launch (2 B l each), the tile's diagonals once (l each as plaintexts, 2 l as
+                // ciphertexts), the outputs once
                 const double nd = (double)(std::min(n, (g0 + ng) * bs) - g0 * bs);
-                ProfScope k(c, "k:k_bsgs_inner_ct", cnt * l * (2.0 * bs + 3.0 * ng) + 2.0 * nd * l);
-                bsgs_inner_ct(c, a, S2, l * N, l * N, S3, l * N, (int)cnt, (int)l);
+                ProfScope k(c, pt ? "k:k_bsgs_inner" : "k:k_bsgs_inner_ct",
+                            pt ? 2.0 * cnt * l * (double)(bs + ng) + nd * l
+                               : cnt * l * (2.0 * bs + 3.0 * ng) + 2.0 * nd * l);
+                bsgs_inner(c, a, !pt, S2, l * N, l * N, Sin, l * N, (int)cnt, (int)l);
             }
-            {  // r_g = relinearize(inner_g), in place in the slot's first two polys; r_0 straight into the accumulator
+            if (!pt) {  // r_g = relinearize(inner_g), in place in the slot's first two polys; r_0 into the accumulator
                 ProfScope pr(c, "bsgs_relin");
                 auto relin = [&](std::size_t t, std::size_t cntk, PolyArr OUT) {
-                    u64 *Tt = T + t * cnt * S3;
-                    keyswitch(c, s, PolyArr{Tt + 2 * l * N, S3, 0}, rk->d, PolyArr{Tt, S3, l * N}, 2, OUT, (int)cntk, (int)l);
+                    keyswitch(c, s, PolyArr{slot(t) + 2 * l * N, S3, 0}, rk->d, PolyArr{slot(t), S3, l * N}, 2, OUT,
+                              (int)cntk, (int)l);
                 };
                 std::size_t t = 0;
                 if (g0 == 0) relin(t++, cnt, PolyArr{A[cur], S2, l * N});
                 if (t < ng && merged(Bc)) {
-                    relin(t, (ng - t) * cnt, PolyArr{T + t * cnt * S3, S3, l * N});
+                    relin(t, (ng - t) * cnt, PolyArr{slot(t), S3, l * N});
                     t = ng;
                 }
-                for (; t < ng; ++t) relin(t, cnt, PolyArr{T + t * cnt * S3, S3, l * N});
+                for (; t < ng; ++t) relin(t, cnt, PolyArr{slot(t), S3, l * N});
             }
             for (std::size_t t = 0; t < ng; ++t) {
                 const std::size_t g = g0 + t;
                 if (g == 0) continue;
-                const PolyArr X{T + t * cnt * S3, S3, l * N};
+                const PolyArr X{slot(t), Sin, l * N};
                 const std::vector<u32> &el = rots.gelts[g];
                 for (std::size_t e = 0; e + 1 < el.size(); ++e)
                     galois_ks(c, s, X, X, (int)cnt, (int)l, el[e], gk->keys.at(el[e]));
@@ -2191,6 +2102,10 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
                 throw std::invalid_argument("option " + n + " takes " + std::to_string(lo) + ".." + std::to_string(hi));
             return (int)value;
         };
+        auto one_of = [&](auto list, const char *takes) {  // a kernel tile: the members of its list (hec_internal.h)
+            if (!list.has(value)) throw std::invalid_argument("option " + n + takes);
+            return (int)value;
+        };
         auto apply = [&](Ctx &c) {
             if (n == "lanes") c.lanes = (int)std::max<int64_t>(1, value);
             else if (n == "lane_min_batch") c.lane_min_batch = (int)std::max<int64_t>(1, value);
@@ -2222,17 +2137,11 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "math_chunk") c.math_chunk = in(0, 65535);
             else if (n == "rot_add") c.rot_add = in(0, 1);
             else if (n == "bsgs_chunk") c.bsgs_chunk = in(0, 65535);
-            else if (n == "bsgs_bg" || n == "bsgs_gg") {
-                const bool bg = n == "bsgs_bg";
-                if (!(value == 2 || value == 4 || (bg ? value == 1 : value == 8 || value == 16)))
-                    throw std::invalid_argument("option " + n + (bg ? " takes 1, 2 or 4" : " takes 2, 4, 8 or 16"));
-                (bg ? c.bsgs_bg : c.bsgs_gg) = (int)value;
-            } else if (n == "bsgs_ct_bg" || n == "bsgs_ct_gg") {
-                const bool bg = n == "bsgs_ct_bg";
-                if (!(value == 2 || (bg ? value == 1 : value == 4 || value == 8)))
-                    throw std::invalid_argument("option " + n + (bg ? " takes 1 or 2" : " takes 2, 4 or 8"));
-                (bg ? c.bsgs_ct_bg : c.bsgs_ct_gg) = (int)value;
-            } else if (n == "bsgs_order") c.bsgs_order = in(0, 1);
+            else if (n == "bsgs_bg") c.bsgs_bg = one_of(BsgsBG{}, " takes 1, 2 or 4");
+            else if (n == "bsgs_gg") c.bsgs_gg = one_of(BsgsGG{}, " takes 2, 4, 8 or 16");
+            else if (n == "bsgs_ct_bg") c.bsgs_ct_bg = one_of(BsgsCtBG{}, " takes 1 or 2");
+            else if (n == "bsgs_ct_gg") c.bsgs_ct_gg = one_of(BsgsCtGG{}, " takes 2, 4 or 8");
+            else if (n == "bsgs_order") c.bsgs_order = in(0, 1);
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -3835,7 +3744,7 @@ int hec_matmul_diagpt_col_bsgs(hec_context *ctx, const hec_plaintext *const *pdi
     return guard([&] {
         set_device(ctx);
         need(pdiags && cols && out, "null argument");
-        bsgs_core(ctx, pdiags, n, bsgs_plan(n, bs), cols, p, gk, out);
+        bsgs_core(ctx, nullptr, pdiags, n, bsgs_plan(n, bs), cols, p, /*rk*/ nullptr, gk, out);
     });
 }
 
@@ -3846,7 +3755,7 @@ int hec_matmul_diag_col_bsgs(hec_context *ctx, const hec_ciphertext *const *diag
     return guard([&] {
         set_device(ctx);
         need(diags && cols && out, "null argument");
-        bsgs_ct_core(ctx, diags, n, bsgs_plan(n, bs), cols, p, rk, gk, out);
+        bsgs_core(ctx, diags, nullptr, n, bsgs_plan(n, bs), cols, p, rk, gk, out);
     });
 }
 

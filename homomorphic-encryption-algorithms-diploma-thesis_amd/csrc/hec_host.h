@@ -239,6 +239,13 @@ void set_device(hec_context *ctx);
 // Calls that take a context: the object must belong to this very context
 void check_obj(const hec_context *ctx, const DevObject *o, const char *msg);
 void check_ct(const hec_context *ctx, const hec_ciphertext *a);
+// The output-alias rule: out[i] may be entry i's own inputs ins[k][i]; an output listed twice, one that
+// is another entry's input, or one of the n_never objects of `never` (inputs that every entry reads) is refused: an
+// output written by one pass must not be an input that a later pass gathers.  ctx non-null: every out[i] is checked as
+// an object of ctx in the loop of the duplicate test, so out = [x, x, invalid] answers "alias"
+void check_out_alias(const std::vector<const hec_ciphertext *const *> &ins, hec_ciphertext *const *out, uint64_t B,
+                     const hec_context *ctx = nullptr, const hec_ciphertext *const *never = nullptr,
+                     uint64_t n_never = 0);
 void d2d(Ctx &c, void *dst, const void *src, std::size_t words);
 // the one output store: grow(o), copy size * level * N words from src, set o's size, level and scale
 void store_ct(Ctx &c, hec_ciphertext *o, const u64 *src, std::size_t size, std::size_t level, double scale);

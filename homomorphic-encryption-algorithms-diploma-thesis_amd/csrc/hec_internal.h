@@ -154,11 +154,11 @@ struct Ctx {
     int bsgs_chunk = 0;            // option "bsgs_chunk": input vectors per pass of the hec_matmul_diag*_col_bsgs calls, 0 automatic
                                    // (the NTT launches' y-blocks and the free device memory bound it).  Same words
     int bsgs_bg = 2, bsgs_gg = 8;  // options "bsgs_bg", "bsgs_gg": k_bsgs_inner's tile, batch entries x giant groups
-                                   // per thread (the instantiations of bsgs_inner()).  Same words
+                                   // per thread (members of BsgsBG, BsgsGG below).  Same words
     int bsgs_order = 1;            // option "bsgs_order": 1 k_bsgs_inner's batch groups of a coefficient block on
                                    // consecutive block ids, 0 coefficient blocks consecutive.  Same words
-    int bsgs_ct_bg = 2, bsgs_ct_gg = 8;  // options "bsgs_ct_bg", "bsgs_ct_gg": k_bsgs_inner_ct's tile (the instantiations
-                                   // of bsgs_inner_ct()).  Same words
+    int bsgs_ct_bg = 2, bsgs_ct_gg = 8;  // options "bsgs_ct_bg", "bsgs_ct_gg": k_bsgs_inner_ct's tile (members of
+                                   // BsgsCtBG, BsgsCtGG below).  Same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -289,8 +289,8 @@ struct TensorBatch {
 void tensor_multi(Ctx &c, const TensorBatch &tb, u64 r_sb, u64 r_sk, u64 a_sk, PolyArr ACC, int B, int l,
                   bool assign, bool plain = false);  // plain: the A_t are plaintexts (ct x pt, 2-poly ACC)
 // the inner sums of the baby-step giant-step ct x pt matvec (k_bsgs_inner): giants g0 .. g0 + ng - 1, ng <=
-// bsgs_tile(c); out[t][b][k] = sum_i P[(g0 + t) bs + i] R[i][b][k] over the babies i < bs with (g0 + t) bs + i < n.
-// R (bs pointers) and P (n pointers) are device tables; R[i][b] at R[i] + b r_sb, polys r_sk apart; out likewise
+// bsgs_tile(c, false); out[t][b][k] = sum_i P[(g0 + t) bs + i] R[i][b][k] over the babies i < bs with
+// (g0 + t) bs + i < n.  R (bs pointers) and P (n pointers) are device tables; R[i][b] at R[i] + b r_sb, polys r_sk apart; out likewise
 constexpr int BSGS_GG_MAX = 16;
 struct BsgsInner {
     const u64 *const *R;
@@ -299,12 +299,22 @@ struct BsgsInner {
     u64 n;
     int bs, g0, ng;
 };
-int bsgs_tile(const Ctx &c);  // giants per k_bsgs_inner launch (option "bsgs_gg")
-void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int l);
-// the ct x ct form (k_bsgs_inner_ct): P holds the n ciphertext diagonals (size 2, polys a_sk apart), out[t][b] the
-// size-3 sum of the tensor products R[i][b] (x) P[(g0 + t) bs + i], polys o_sk apart; ng <= bsgs_ct_tile(c)
-int bsgs_ct_tile(const Ctx &c);  // giants per k_bsgs_inner_ct launch (option "bsgs_ct_gg")
-void bsgs_inner_ct(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l);
+// ct: the ct x ct form (k_bsgs_inner_ct): P holds the n ciphertext diagonals (size 2, polys a_sk apart; the ct x pt
+// form does not read a_sk), out[t][b] the size-3 sum of the tensor products R[i][b] (x) P[(g0 + t) bs + i], polys o_sk
+// apart; ng <= bsgs_tile(c, true)
+//
+// The tiles (BG batch entries x GG giant groups per thread) each form's kernel is instantiated for: the dispatch of
+// bsgs_inner() is generated from these lists and hec_context_set_option accepts exactly their members
+template <int... V>
+struct IntList {
+    static constexpr bool has(int64_t v) { return ((v == V) || ...); }
+};
+using BsgsBG = IntList<1, 2, 4>;
+using BsgsGG = IntList<2, 4, 8, 16>;
+using BsgsCtBG = IntList<1, 2>;
+using BsgsCtGG = IntList<2, 4, 8>;
+int bsgs_tile(const Ctx &c, bool ct);  // giants per launch (option "bsgs_gg", ct: "bsgs_ct_gg")
+void bsgs_inner(Ctx &c, const BsgsInner &a, bool ct, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l);
 void tensor_sum(Ctx &c, PolyArr R, PolyArr A, u64 *ACC, u64 acc_sk, int B, int l);
 void ew_add(Ctx &c, PolyArr a, PolyArr b, PolyArr out, int B, int nk, int nl, int mode);  // 0 add, 1 sub
 void ew_negate(Ctx &c, PolyArr a, int B, int nk, int nl);

@@ -4011,37 +4011,7 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-int bsgs_tile(const Ctx &c) { return c.bsgs_gg; }
-
-void bsgs_inner(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 o_sb, u64 o_sk, int B, int l)
-{
-    if (a.ng < 1 || a.ng > c.bsgs_gg || a.bs < 1 || B < 1) throw std::logic_error("bsgs_inner: bad tile");
-    const u64 total = (u64)l * c.N;
-    const int BG = c.bsgs_bg, ncb = (int)((total + 255) / 256), nbg = (B + BG - 1) / BG;
-    const dim3 grid((unsigned)((u64)ncb * (u64)nbg));
-#define HEC_BSGS(BGv, GGv)                                                                                         \
-    k_bsgs_inner<BGv, GGv><<<grid, 256, 0, c.stream>>>(a, r_sb, r_sk, o_sb, o_sk, B, c.logN, total, c.primes, nbg, \
-                                                       ncb, c.bsgs_order)
-    switch (BG * 32 + c.bsgs_gg) {
-    case 1 * 32 + 2: HEC_BSGS(1, 2); break;
-    case 1 * 32 + 4: HEC_BSGS(1, 4); break;
-    case 1 * 32 + 8: HEC_BSGS(1, 8); break;
-    case 1 * 32 + 16: HEC_BSGS(1, 16); break;
-    case 2 * 32 + 2: HEC_BSGS(2, 2); break;
-    case 2 * 32 + 4: HEC_BSGS(2, 4); break;
-    case 2 * 32 + 8: HEC_BSGS(2, 8); break;
-    case 2 * 32 + 16: HEC_BSGS(2, 16); break;
-    case 4 * 32 + 2: HEC_BSGS(4, 2); break;
-    case 4 * 32 + 4: HEC_BSGS(4, 4); break;
-    case 4 * 32 + 8: HEC_BSGS(4, 8); break;
-    case 4 * 32 + 16: HEC_BSGS(4, 16); break;
-    default: throw std::logic_error("bsgs_inner: no kernel for this tile");
-    }
-#undef HEC_BSGS
-    HEC_HIP(hipGetLastError());
-}
-
-// The inner sums of the baby-step giant-step ct x ct matvec (hec_engine.hip bsgs_ct_core) for a tile of ng <= GG giant
+// The inner sums of the baby-step giant-step ct x ct matvec (hec_engine.hip bsgs_core) for a tile of ng <= GG giant
 // groups in one launch: the size-3 tensor products of the baby rotations with the ciphertext diagonals, summed,
 //   OUT_t[b][0] = sum_i R_i[b][0] A'_j[0]
 //   OUT_t[b][1] = sum_i (R_i[b][0] A'_j[1] + R_i[b][1] A'_j[0])
@@ -4155,28 +4125,36 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-int bsgs_ct_tile(const Ctx &c) { return c.bsgs_ct_gg; }
+int bsgs_tile(const Ctx &c, bool ct) { return ct ? c.bsgs_ct_gg : c.bsgs_gg; }
 
-void bsgs_inner_ct(Ctx &c, const BsgsInner &a, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l)
+// launch(BG, GG), as integral constants, for the members of the two lists that equal (bg, gg); false: there are none
+template <int... BGs, int... GGs, class F>
+bool bsgs_dispatch(IntList<BGs...>, IntList<GGs...>, int bg, int gg, F launch)
 {
-    if (a.ng < 1 || a.ng > c.bsgs_ct_gg || a.bs < 1 || a.bs > 512 || B < 1)
-        throw std::logic_error("bsgs_inner_ct: bad tile");
+    auto row = [&](auto BG) { return ((gg == GGs && (launch(BG, std::integral_constant<int, GGs>{}), true)) || ...); };
+    return ((bg == BGs && row(std::integral_constant<int, BGs>{})) || ...);
+}
+
+// one launcher for both forms: the kernel of the form, instantiated over the form's tile lists (hec_internal.h)
+void bsgs_inner(Ctx &c, const BsgsInner &a, bool ct, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l)
+{
+    const int BG = ct ? c.bsgs_ct_bg : c.bsgs_bg, GG = bsgs_tile(c, ct);
+    if (a.ng < 1 || a.ng > GG || a.bs < 1 || (ct && a.bs > 512) || B < 1)
+        throw std::logic_error(ct ? "bsgs_inner_ct: bad tile" : "bsgs_inner: bad tile");
     const u64 total = (u64)l * c.N;
-    const int BG = c.bsgs_ct_bg, ncb = (int)((total + 255) / 256), nbg = (B + BG - 1) / BG;
+    const int ncb = (int)((total + 255) / 256), nbg = (B + BG - 1) / BG;
     const dim3 grid((unsigned)((u64)ncb * (u64)nbg));
-#define HEC_BSGS_CT(BGv, GGv)                                                                                      \
-    k_bsgs_inner_ct<BGv, GGv><<<grid, 256, 0, c.stream>>>(a, r_sb, r_sk, a_sk, o_sb, o_sk, B, c.logN, total, c.primes, \
-                                                          nbg, ncb, c.bsgs_order)
-    switch (BG * 32 + c.bsgs_ct_gg) {
-    case 1 * 32 + 2: HEC_BSGS_CT(1, 2); break;
-    case 1 * 32 + 4: HEC_BSGS_CT(1, 4); break;
-    case 1 * 32 + 8: HEC_BSGS_CT(1, 8); break;
-    case 2 * 32 + 2: HEC_BSGS_CT(2, 2); break;
-    case 2 * 32 + 4: HEC_BSGS_CT(2, 4); break;
-    case 2 * 32 + 8: HEC_BSGS_CT(2, 8); break;
-    default: throw std::logic_error("bsgs_inner_ct: no kernel for this tile");
-    }
-#undef HEC_BSGS_CT
+    const bool found =
+        ct ? bsgs_dispatch(BsgsCtBG{}, BsgsCtGG{}, BG, GG, [&](auto bg, auto gg) {
+                 k_bsgs_inner_ct<decltype(bg)::value, decltype(gg)::value><<<grid, 256, 0, c.stream>>>(
+                     a, r_sb, r_sk, a_sk, o_sb, o_sk, B, c.logN, total, c.primes, nbg, ncb, c.bsgs_order);
+             })
+           : bsgs_dispatch(BsgsBG{}, BsgsGG{}, BG, GG, [&](auto bg, auto gg) {
+                 k_bsgs_inner<decltype(bg)::value, decltype(gg)::value><<<grid, 256, 0, c.stream>>>(
+                     a, r_sb, r_sk, o_sb, o_sk, B, c.logN, total, c.primes, nbg, ncb, c.bsgs_order);
+             });
+    if (!found)
+        throw std::logic_error(ct ? "bsgs_inner_ct: no kernel for this tile" : "bsgs_inner: no kernel for this tile");
     HEC_HIP(hipGetLastError());
 }
 

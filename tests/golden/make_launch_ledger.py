@@ -37,6 +37,13 @@ class Env:
             out.append(self.ctx.ciphertext().fill_uniform(size, level, scale, self.seed))
         return out
 
+    def pts(self, count, level=LEVEL, scale=SCALE):
+        out = []
+        for _ in range(count):
+            self.seed += 1
+            out.append(self.ctx.plaintext(None, scale).fill_uniform(level, scale, self.seed))
+        return out
+
 
 def _chunked(fn):
     def run(e):
@@ -46,6 +53,29 @@ def _chunked(fn):
         finally:
             e.ctx.set_option("math_chunk", 0)
     return run
+
+
+def _bsgs_small(gg_option, fn):
+    """the call with 2 giants per tile and 2 input vectors per pass: G = 3 in tiles {0, 1} and {2}, p = 3 in passes of
+    2 and 1"""
+    def run(e):
+        e.ctx.set_option(gg_option, 2)
+        e.ctx.set_option("bsgs_chunk", 2)
+        try:
+            fn(e)
+        finally:
+            e.ctx.set_option(gg_option, 8)
+            e.ctx.set_option("bsgs_chunk", 0)
+    return run
+
+
+# n = 10, bs = 4: G = 3, step 3 is a NAF chain on the keys of STEPS; p = 3 leaves a partial batch group at BG = 2
+def _bsgs_pt(e):
+    e.ctx.matmul_diagpt_col_bsgs(e.pts(10), e.cts(3), e.gk, bs=4)
+
+
+def _bsgs_ct(e):
+    e.ctx.matmul_diag_col_bsgs(e.cts(10), e.cts(3), e.rk, e.gk, bs=4)
 
 
 def _partial_finish(e):
@@ -85,6 +115,10 @@ CALLS = {
     "matrix_matmul_2x2": lambda e: e.ctx.matrix_matmul(e.cts(4), 2, 2, 0, e.cts(4), 2, 2, 0, e.rk),
     "relinearize_inplace": lambda e: e.ctx.relinearize(e.cts(1, size=3)[0], e.rk),
     "rescale_to_next_inplace": lambda e: e.ctx.rescale_to_next(e.cts(1)[0]),
+    "bsgs_pt_n10_p3_bs4": _bsgs_pt,
+    "bsgs_ct_n10_p3_bs4": _bsgs_ct,
+    "bsgs_pt_n10_p3_bs4_gg2_chunk2": _bsgs_small("bsgs_gg", _bsgs_pt),
+    "bsgs_ct_n10_p3_bs4_gg2_chunk2": _bsgs_small("bsgs_ct_gg", _bsgs_ct),
 }
 
 

@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
-"""The baby-step giant-step ct x pt matvec (hec_matmul_diagpt_col_bsgs) against the reference schedule
-(hec_matmul_diagpt_col) at cfg3: N = 2^15, {60, 40 x 9, 60}, level 10, n = 4096, scale 2^40, on uniform synthetic
-plaintexts, ciphertexts and keys.  Sides, all in one process, alternated, timed with HIP events on the context's
-stream after a warm-up of every side:
-  bsgs32 / bsgs64 / bsgs128   bs = 32, 64, 128 with a Galois key for every planned step
-  bsgs64_default              bs = 64 on the default (power-of-two) key set: NAF chains
-  reference                   hec_matmul_diagpt_col on the default key set
-The sides do not share their ciphertext bits (tests/test_gpu_bsgs.py checks each against the oracle), so nothing is
-compared here but the tile variants of k_bsgs_inner with the default tile, word for word on three outputs.
+"""The baby-step giant-step matvec against the reference schedule at cfg3: N = 2^15, {60, 40 x 9, 60}, level 10,
+n = 4096, scale 2^40, on uniform synthetic diagonals, ciphertexts and keys.  --form pt: hec_matmul_diagpt_col_bsgs
+against hec_matmul_diagpt_col (plaintext diagonals); --form ct: hec_matmul_diag_col_bsgs against hec_matmul_diag_col
+(ciphertext diagonals, a relinearisation key).  Sides, all in one process, alternated, timed with HIP events on the
+context's stream after a warm-up of every side:
+  bsgs32 / bsgs64 / bsgs128 [/ bsgs256 for ct]   that bs with a Galois key for every planned step
+  bsgs64_default                                  bs = 64 on the default (power-of-two) key set: NAF chains
+  reference                                       the reference schedule on the default key set
+The sides do not share their ciphertext bits (tests/test_gpu_bsgs.py and tests/test_gpu_bsgs_ctct.py check each against
+the oracle), so nothing is compared here but the tile variants of the form's inner-sum kernel with the default tile,
+word for word on three outputs.
 Prints one JSON line: matvec/s per side (median of the repetitions, spread = (max - min) / median), the key switches
-per input vector from the plans, the per-class table of bs = 64 from a separate profiled run (each kernel class's ms,
-GB/s on its algorithmic bytes and share of the call), and k_bsgs_inner's time per tile (options "bsgs_bg", "bsgs_gg",
-"bsgs_order") from profiled runs of their own.
+per input vector from the plans (ct: rotations + relinearisations), the per-class table of bs = 64 from a separate
+profiled run (each kernel class's ms, GB/s on its algorithmic bytes and share of the call; ct: also the inner and
+relinearisation scopes), and the inner-sum kernel's time per tile (options "bsgs_bg", "bsgs_gg" or "bsgs_ct_bg",
+"bsgs_ct_gg", and "bsgs_order") from profiled runs of their own.
 
-    python tools/bsgs_bench.py [--b 128] [--n 4096] [--reps 3] [--out profiles/bsgs_bench.json]
+    python tools/bsgs_bench.py --form pt [--b 128] [--n 4096] [--reps 3] [--out profiles/bsgs_bench.json]
+    python tools/bsgs_bench.py --form ct [--b 128] [--n 4096] [--reps 3] [--out profiles/bsgs_ctct_bench.json]
 """
 import argparse
 import json
@@ -26,12 +30,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 N, BITS, SCALE = 1 << 15, [60] + [40] * 9 + [60], 2.0**40
-TILES = [(2, 8, 1), (2, 8, 0), (2, 4, 1), (2, 2, 1), (1, 8, 1), (4, 4, 1), (4, 8, 1)]  # (bg, gg, order); first = default
+# per form: the log prefix, the block sizes, the inner-sum kernel, the tile options and the tiles (bg, gg, order), the
+# default tile first
+FORMS = {
+    "pt": dict(tag="bsgs_bench", block_sizes=(32, 64, 128), kernel="k_bsgs_inner",
+               opts=("bsgs_bg", "bsgs_gg", "bsgs_order"),
+               tiles=[(2, 8, 1), (2, 8, 0), (2, 4, 1), (2, 2, 1), (1, 8, 1), (4, 4, 1), (4, 8, 1)]),
+    "ct": dict(tag="bsgs_ctct_bench", block_sizes=(32, 64, 128, 256), kernel="k_bsgs_inner_ct",
+               opts=("bsgs_ct_bg", "bsgs_ct_gg", "bsgs_order"),
+               tiles=[(2, 8, 1), (2, 8, 0), (2, 4, 1), (2, 2, 1), (1, 2, 1), (1, 4, 1), (1, 8, 1)]),
+}
 
 
 def default_key_switches(n, bs):
-    """Key switches per input vector on the default key set: the distinct prefixes of the babies' NAF chains (the
-    rotation trie) and every element of the giants' chains."""
+    """Rotation key switches per input vector on the default key set: the distinct prefixes of the babies' NAF chains
+    (the rotation trie) and every element of the giants' chains."""
     from _helpers import rotation_seq
     pre = set()
     for i in range(1, min(bs, n)):
@@ -43,16 +56,21 @@ def default_key_switches(n, bs):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--form", choices=sorted(FORMS), required=True,
+                    help="pt: plaintext diagonals, ct: ciphertext diagonals")
     ap.add_argument("--b", type=int, default=128, help="input vectors per call")
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3, help="timed runs of each side, alternated (at least 3)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     reps, B, n = max(3, args.reps), args.b, args.n
+    ct = args.form == "ct"
+    form = FORMS[args.form]
+    tag, block_sizes, kernel, opts, tiles = (form[k] for k in ("tag", "block_sizes", "kernel", "opts", "tiles"))
 
     import torch
     if not torch.cuda.is_available():  # one HIP runtime for torch and the engine; no device, no measurement
-        print("bsgs_bench: no GPU", file=sys.stderr)
+        print(f"{tag}: no GPU", file=sys.stderr)
         return 1
     from _helpers import load_hecdna, rotation_trie_stats
     hec = load_hecdna()
@@ -60,25 +78,35 @@ def main():
     stream = torch.cuda.Stream()
     ctx.set_stream(stream.cuda_stream)
     L = len(BITS) - 1
-    pts = [hec.Plaintext(ctx, None, SCALE).fill_uniform(L, SCALE, 20000 + j) for j in range(n)]
+    if ct:
+        diags = [hec.Ciphertext(ctx).fill_uniform(2, L, SCALE, 20000 + j) for j in range(n)]
+    else:
+        diags = [hec.Plaintext(ctx, None, SCALE).fill_uniform(L, SCALE, 20000 + j) for j in range(n)]
     xs = [hec.Ciphertext(ctx).fill_uniform(2, L, SCALE, 1000 + i) for i in range(B)]
-    block_sizes = (32, 64, 128)
     steps = sorted({s for bs in block_sizes for s in hec.bsgs_plan(n, bs)[1]})
-    gk_steps = ctx.galois_keys(uniform_elts=[ctx.elt_from_step(s) for s in steps], seed=77)  # a key per step of all three
+    gk_steps = ctx.galois_keys(uniform_elts=[ctx.elt_from_step(s) for s in steps], seed=77)  # a key per step of all
     gk_def = ctx.galois_keys(uniform_elts=ctx.default_galois_elts(), seed=78)
+    if ct:
+        rk = ctx.relin_key(seed=79)
+        bsgs = lambda gk, bs, o: ctx.matmul_diag_col_bsgs(diags, xs, rk, gk, bs=bs, out=o)  # noqa: E731
+        reference = lambda o: ctx.matmul_diag_col(diags, xs, rk, gk_def, out=o)  # noqa: E731
+    else:
+        bsgs = lambda gk, bs, o: ctx.matmul_diagpt_col_bsgs(diags, xs, gk, bs=bs, out=o)  # noqa: E731
+        reference = lambda o: ctx.matmul_diagpt_col(diags, xs, gk_def, out=o)  # noqa: E731
     outs = {}  # every side writes into its own outputs: no allocation in the timed calls
 
     def side(name, fn):
         outs[name] = [hec.Ciphertext(ctx) for _ in range(B)]
         return lambda: fn(outs[name])
 
-    sides = {f"bsgs{bs}": side(f"bsgs{bs}", lambda o, bs=bs: ctx.matmul_diagpt_col_bsgs(pts, xs, gk_steps, bs=bs, out=o))
-             for bs in block_sizes}
-    sides["bsgs64_default"] = side("bsgs64_default", lambda o: ctx.matmul_diagpt_col_bsgs(pts, xs, gk_def, bs=64, out=o))
-    sides["reference"] = side("reference", lambda o: ctx.matmul_diagpt_col(pts, xs, gk_def, out=o))
-    ks = {f"bsgs{bs}": len(hec.bsgs_plan(n, bs)[1]) for bs in block_sizes}
-    ks["bsgs64_default"] = default_key_switches(n, 64)
-    ks["reference"] = rotation_trie_stats(N, n)[0]
+    sides = {f"bsgs{bs}": side(f"bsgs{bs}", lambda o, bs=bs: bsgs(gk_steps, bs, o)) for bs in block_sizes}
+    sides["bsgs64_default"] = side("bsgs64_default", lambda o: bsgs(gk_def, 64, o))
+    sides["reference"] = side("reference", reference)
+    # ct: one relinearisation per giant group on top of the rotations, one for the reference
+    relins = (lambda bs: -(-n // min(bs, n))) if ct else (lambda bs: 0)
+    ks = {f"bsgs{bs}": len(hec.bsgs_plan(n, bs)[1]) + relins(bs) for bs in block_sizes}
+    ks["bsgs64_default"] = default_key_switches(n, 64) + relins(64)
+    ks["reference"] = rotation_trie_stats(N, n)[0] + (1 if ct else 0)
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -92,12 +120,12 @@ def main():
     for k, fn in sides.items():  # warm-up of every side: workspace, output buffers, per-key tables
         fn()
         ctx.synchronize()
-        print(f"bsgs_bench: warmed {k}", file=sys.stderr, flush=True)
+        print(f"{tag}: warmed {k}", file=sys.stderr, flush=True)
     times = {k: [] for k in sides}
     for _ in range(reps):  # alternated
         for k, fn in sides.items():
             times[k].append(timed(fn))
-            print(f"bsgs_bench: {k} {times[k][-1]:.1f} ms", file=sys.stderr, flush=True)
+            print(f"{tag}: {k} {times[k][-1]:.1f} ms", file=sys.stderr, flush=True)
     result = {"N": N, "moduli_bits": BITS, "level": L, "n": n, "B": B, "reps": reps, "sides": {}}
     for k, ms in times.items():
         med = float(np.median(ms))
@@ -121,26 +149,29 @@ def main():
         cls: {"ms": round(ms, 3), "launches": kl, "share": round(ms / call_ms, 4),
               "GBps": round(nb / (ms * 1e-3) / 1e9, 1) if ms and nb else None}
         for cls, (ms, _scopes, nb, kl) in sorted(tab.items()) if cls.startswith("k:")}}
+    if ct:
+        result["bsgs64_classes"]["scopes"] = {cls: round(tab[cls][0], 3) for cls in ("bsgs_inner_ct", "bsgs_relin")
+                                              if cls in tab}
 
-    # k_bsgs_inner per tile at bs = 64, and the outputs of every tile against the default tile's
+    # the inner-sum kernel per tile at bs = 64, and the outputs of every tile against the default tile's
     want = [outs["bsgs64"][i].download() for i in (0, B // 2, B - 1)]
     result["tiles"], equal = [], True
-    for bg, gg, order in TILES:
-        for k, v in (("bsgs_bg", bg), ("bsgs_gg", gg), ("bsgs_order", order)):
+    for tile in tiles:
+        for k, v in zip(opts, tile):
             ctx.set_option(k, v)
         sides["bsgs64"]()  # warm-up: the tile changes the workspace
         runs = []
         for _ in range(reps):
             ms_call, t = profiled(sides["bsgs64"])
-            ms, _scopes, nb, kl = t["k:k_bsgs_inner"]
+            ms, _scopes, nb, kl = t["k:" + kernel]
             runs.append((ms, nb, kl, ms_call))
         ms, nb, kl, ms_call = sorted(runs)[len(runs) // 2]
         equal = equal and all(np.array_equal(outs["bsgs64"][i].download(), w) for i, w in zip((0, B // 2, B - 1), want))
-        print(f"bsgs_bench: tile {bg}x{gg} order {order}: k_bsgs_inner {ms:.2f} ms", file=sys.stderr, flush=True)
-        result["tiles"].append({"bg": bg, "gg": gg, "order": order, "k_bsgs_inner_ms": round(ms, 3), "launches": kl,
-                                "GBps": round(nb / (ms * 1e-3) / 1e9, 1), "call_ms": round(ms_call, 2),
+        print(f"{tag}: tile {tile[0]}x{tile[1]} order {tile[2]}: {kernel} {ms:.2f} ms", file=sys.stderr, flush=True)
+        result["tiles"].append({"bg": tile[0], "gg": tile[1], "order": tile[2], kernel + "_ms": round(ms, 3),
+                                "launches": kl, "GBps": round(nb / (ms * 1e-3) / 1e9, 1), "call_ms": round(ms_call, 2),
                                 "spread": round((max(r[0] for r in runs) - min(r[0] for r in runs)) / ms, 4)})
-    for k, v in (("bsgs_bg", TILES[0][0]), ("bsgs_gg", TILES[0][1]), ("bsgs_order", TILES[0][2])):
+    for k, v in zip(opts, tiles[0]):
         ctx.set_option(k, v)
     result["tiles_equal"] = bool(equal)
     line = json.dumps(result)

@@ -1,11 +1,16 @@
-"""The decryption error of the baby-step giant-step ct x pt matvec against the reference schedule's, on the CPU
-with the oracle alone (no device): for five seeds, the max-abs error over the n output slots of the oracle's
-matmul_diagpt_col_set (the reference loop) and of the BSGS composition (rotate, multiply_plain, add, rescale in the
-schedule's order) on the same matrix, vectors, keys and encryptions.  tests/test_gpu_bsgs.py bounds the GPU result's
-error by m times the reference schedule's, m = twice the worst ratio printed here.
+"""The decryption error of the baby-step giant-step matvec against the reference schedule's, on the CPU with the
+oracle alone (no device): for five seeds, the max-abs error over the n output slots of the reference loop and of the
+BSGS composition on the same matrix, vectors, keys and encryptions.
+  --form pt   the oracle's matmul_diagpt_col_set against rotate, multiply_plain, add, rescale in the schedule's order;
+              tests/test_gpu_bsgs.py bounds the GPU result's error by m times the reference schedule's
+  --form ct   the oracle's matmul_diag_col against rotate, multiply, add, relinearize, rotate, add, rescale; the BSGS
+              diagonals encrypt the rolled slot vectors with the seeds of the natural ones; tests/test_gpu_bsgs_ctct.py
+              bounds the error likewise
+m = twice the worst ratio printed here.
 
-    python tools/bsgs_error.py            # N = 2^11, [50, 36, 36, 50], n = 24, bs = 8, p = 3, default Galois keys
+    python tools/bsgs_error.py --form pt  # N = 2^11, [50, 36, 36, 50], n = 24, bs = 8, p = 3, default Galois keys
 """
+import argparse
 import json
 import os
 import sys
@@ -20,6 +25,10 @@ N, BITS, n, bs, p, SCALE = 1 << 11, [50, 36, 36, 50], 24, 8, 3, 2.0**40
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--form", choices=("ct", "pt"), required=True,
+                    help="pt: plaintext diagonals, ct: ciphertext diagonals")
+    ct = ap.parse_args().form == "ct"
     orc = load_oracle()
     m = orc.Oracle.create_coeff_modulus(N, BITS)
     o = orc.Oracle(N, m)
@@ -29,15 +38,23 @@ def main():
     for seed in range(5):
         rng = np.random.default_rng(100 + seed)
         sk = o.secret_key(seed + 1)
+        rk = o.relin_key(sk, seed + 30) if ct else None
         gk = o.galois_keys(sk, o.default_galois_elts(), seed + 50)
         M = rng.uniform(-1, 1, (n, n))
         xs = rng.uniform(-1, 1, (p, n))
         D = diag_vectors(M, slots)
         X = [o.encrypt(sk, o.encode(col_vector(x, slots), SCALE, L), SCALE, 900 + 10 * seed + i)
              for i, x in enumerate(xs)]
-        P = [o.encode(d, SCALE, L) for d in D]
-        Pb = [o.encode(np.roll(D[j], (j // bs) * bs), SCALE, L) for j in range(n)]
-        ref = o.matmul_diagpt_col_set(P, SCALE, list(range(n)), X, gk)
+        rolled = [np.roll(D[j], (j // bs) * bs) for j in range(n)]  # the BSGS form of the diagonals
+        if ct:
+            enc = lambda d, j: o.encrypt(sk, o.encode(d, SCALE, L), SCALE, 5000 + 100 * seed + j)  # noqa: E731
+            Db = [enc(rolled[j], j) for j in range(n)]
+            ref = o.matmul_diag_col([enc(D[j], j) for j in range(n)], X, rk, gk)
+            term = lambda r, d: o.multiply(r, d)  # noqa: E731
+        else:
+            Db = [o.encode(d, SCALE, L) for d in rolled]
+            ref = o.matmul_diagpt_col_set([o.encode(d, SCALE, L) for d in D], SCALE, list(range(n)), X, gk)
+            term = lambda r, d: o.multiply_plain(r, d, SCALE)  # noqa: E731
         e_ref = e_bsgs = 0.0
         for i, x in enumerate(X):
             rots = [x] + [o.rotate(x, k, gk) for k in range(1, bs)]
@@ -47,9 +64,10 @@ def main():
                 for k in range(bs):
                     if g * bs + k >= n:
                         break
-                    t = o.multiply_plain(rots[k], Pb[g * bs + k], SCALE)
+                    t = term(rots[k], Db[g * bs + k])
                     inner = t if inner is None else o.add(inner, t)
-                r = inner if g == 0 else o.rotate(inner, g * bs, gk)
+                r = o.relinearize(inner, rk) if ct else inner
+                r = r if g == 0 else o.rotate(r, g * bs, gk)
                 acc = r if acc is None else o.add(acc, r)
             out = o.rescale(acc)
             want = M @ xs[i]
