@@ -1204,8 +1204,18 @@ void ntt_strided(Ctx &c, bool inverse, const u64 *src, u64 ps_src, u64 *dst, u64
     else ntt_dispatch<false>(c, njobs, first, second, stages);
 }
 
+// The mod-up passes that put one job per (b, I, J) along y: B l l blocks, which nothing above them splits (the fan-out
+// and the fused pass B have B l and a 1-D grid).  At l = 32 that is B <= 63
+static void modup_jobs_fit(int B, int l)
+{
+    if ((long long)B * l * l > 65535)
+        throw std::invalid_argument("key switch: too many ciphertexts for one mod-up pass (B l l jobs, at most 65535 "
+                                    "blocks along y)");
+}
+
 void ks_modup(Ctx &c, const u64 *D, u64 *E, int B, int l, int stages, bool mform)
 {
+    modup_jobs_fit(B, l);
     ModUpMap m{l, c.logN, (int)c.K - 1};
     ModUpIO_A a{m, D, E, c.primes};
     if (c.nt_e) {
@@ -3383,7 +3393,7 @@ __device__ __forceinline__ void bmac_body(u64 *lds, u64 *ltw, u64 *ltwa, PolyArr
                 f0[e] += fp_mulmod(dv, u2d(k0[e]), pr.qd, pr.qinv);
                 f1[e] += fp_mulmod(dv, u2d(k1[e]), pr.qd, pr.qinv);
             } else {
-                mac128(i0[e], v[e], k0[e]);  // v < 4q: sum of l products < 2^126
+                mac128(i0[e], v[e], k0[e]);  // v < 4q < 2^62, key < 2^60: sum of l <= 32 products < 2^127
                 mac128(i1[e], v[e], k1[e]);
             }
         }
@@ -3549,6 +3559,7 @@ static void run_modup_fused(Ctx &c, const u64 *D, u64 *E, PolyArr T, const u64 *
     const TwTables fwd{c.tw, c.twb, c.twf, c.twbf, c.tws, c.twbs};
     // (2a) pass A of every mod-up NTT (B * l * l jobs), output E[b][I][J] (lazy, pass-A domain)
     if (part & 1) {
+        modup_jobs_fit(B, l);
         ModUpMap m{l, c.logN, (int)c.K - 1};
         k_ntt<LOGR, NA, false, true, false><<<dim3(C / NA, B * l * l), NA * R / 16, 0, c.stream>>>(
             ModUpIO_A{m, D, E, c.primes}, fwd, c.primes, c.logN);
