@@ -112,6 +112,8 @@ def lib():
             "hec_matmul_diag_col_partial_set": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp],
             "hec_matmul_finish": [vp, vp, C.c_uint64, vp, vp],
             "hec_matmul_col_colT": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp],
+            "hec_colcolT_bsgs_plan": [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int), C.c_uint64, u64p, u64p],
+            "hec_matmul_col_colT_bsgs": [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp, vp],
             "hec_matrix_matmul": [vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int,
                                   vp, vp],
             "hec_ntt_forward": [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64],
@@ -232,7 +234,7 @@ def exported_symbols():
     """Names declared in include/hecdna.h (for the C-ABI export test)."""
     import re
     txt = open(HEADER_PATH).read()
-    return sorted(set(re.findall(r"\b(hec_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(hec_[A-Za-z0-9_]+)\s*\(", txt)))
 
 
 def plan_diagonal_shards(N, n, world, key_elts):
@@ -518,6 +520,23 @@ def bsgs_plan(n, bs=None):
     _check(lib().hec_bsgs_plan(int(n), b, None, 0, C.byref(cnt), C.byref(eff)))
     buf = (C.c_int * max(1, cnt.value))()
     _check(lib().hec_bsgs_plan(int(n), b, buf, cnt.value, C.byref(cnt), C.byref(eff)))
+    return eff.value, list(buf[:cnt.value])
+
+
+DIAG_NATURAL, DIAG_BSGS = 0, 1  # include/hecdna.h HEC_DIAG_NATURAL, HEC_DIAG_BSGS
+
+
+def colcolT_bsgs_plan(p, bs=None, form=0):
+    """hec_colcolT_bsgs_plan (host only): (bs_eff, steps) of Context.matmul_col_colT_bsgs for p output diagonals: the
+    baby steps 1 .. bs_eff - 1, the negative giant steps -g * bs_eff and, for form 0 (natural-form outputs) only, the
+    positive giant steps g * bs_eff.  bs=None picks the smallest power of two >= sqrt(p)."""
+    cnt, eff = C.c_uint64(), C.c_uint64()
+    b = 0 if bs is None else int(bs)
+    if bs is not None and b < 1:
+        raise InvalidArgument(HEC_EINVAL, "bs must be positive")
+    _check(lib().hec_colcolT_bsgs_plan(int(p), b, int(form), None, 0, C.byref(cnt), C.byref(eff)))
+    buf = (C.c_int * max(1, cnt.value))()
+    _check(lib().hec_colcolT_bsgs_plan(int(p), b, int(form), buf, cnt.value, C.byref(cnt), C.byref(eff)))
     return eff.value, list(buf[:cnt.value])
 
 
@@ -963,6 +982,22 @@ class Context:
         out = [Ciphertext(self) for _ in range(p)]
         _check(lib().hec_matmul_col_colT(self.h, self._arr(A), len(A), self._arr(B), p, rk.h, gk.h,
                                          self._arr(out)))
+        return out
+
+    def matmul_col_colT_bsgs(self, A, B, p, rk, gk, bs=None, bsgs_form=False, out=None):
+        """hec_matmul_col_colT_bsgs: matmul_col_colT's product from (bs_eff - 1) baby rotations of every B[j] and
+        ceil(p / bs_eff) - 1 giant rotations of every A[j].  bsgs_form=False: the p diagonals in natural form, as
+        matmul_col_colT gives them (one more rotation per output past the first block).  bsgs_form=True: diagonal i
+        rotated right by (i // bs_eff) * bs_eff slots, what matmul_diag_col_bsgs takes for the same bs, with no
+        rotation of the outputs at all.  Its ciphertext bits are those of the per-operation composition in the
+        schedule's order, not matmul_col_colT's (they coincide for bs >= p)."""
+        out = out or [Ciphertext(self) for _ in range(p)]
+        b = 0 if bs is None else int(bs)
+        if bs is not None and b < 1:
+            raise InvalidArgument(HEC_EINVAL, "bs must be positive")
+        form = bsgs_form if isinstance(bsgs_form, int) and not isinstance(bsgs_form, bool) else int(bool(bsgs_form))
+        _check(lib().hec_matmul_col_colT_bsgs(self.h, self._arr(A), len(A), self._arr(B), int(p), b, form, rk.h, gk.h,
+                                              self._arr(out)))
         return out
 
     def matrix_matmul(self, A, ar, ac, atr, B, br, bc, btr, rk):

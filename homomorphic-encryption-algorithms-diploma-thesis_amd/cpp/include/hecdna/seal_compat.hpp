@@ -890,6 +890,42 @@ inline std::vector<Ciphertext> matmul_diag_col_bsgs(const Evaluator &eval, const
                                    gk.get(), po.data()));
     return out;
 }
+
+// BatchedMatrix::matmul's col x col^T product on the same schedule (hec_matmul_col_colT_bsgs): out[i] for i < p from
+// (bs_eff - 1) baby rotations of every B[j] and ceil(p / bs_eff) - 1 giant rotations of every A[j].  form
+// HEC_DIAG_NATURAL gives the diagonals as BatchedMatrix::matmul does (NOT its ciphertext bits unless bs_eff = p);
+// form HEC_DIAG_BSGS gives diagonal i rotated right by (i / bs_eff) bs_eff slots, which matmul_diag_col_bsgs() above
+// takes for the same bs, and rotates no output.  colcolT_bsgs_steps() lists the rotation steps of a form.
+inline std::vector<int> colcolT_bsgs_steps(std::size_t p, std::size_t bs = 0, int form = HEC_DIAG_NATURAL,
+                                           std::size_t *bs_eff = nullptr)
+{
+    std::uint64_t count = 0, eff = 0;
+    check(hec_colcolT_bsgs_plan(p, bs, form, nullptr, 0, &count, &eff));
+    std::vector<int> steps(count);
+    check(hec_colcolT_bsgs_plan(p, bs, form, steps.data(), count, &count, &eff));
+    if (bs_eff) *bs_eff = eff;
+    return steps;
+}
+inline std::vector<Ciphertext> matmul_col_colT_bsgs(const Evaluator &eval, const std::vector<Ciphertext> &A,
+                                                    const std::vector<Ciphertext> &B, std::size_t p,
+                                                    const RelinKeys &rk, const GaloisKeys &gk, std::size_t bs = 0,
+                                                    int form = HEC_DIAG_NATURAL)
+{
+    if (A.size() != B.size()) throw std::invalid_argument("dimension mismatch");
+    std::vector<const hec_ciphertext *> pa, pb;
+    for (const auto &a : A) pa.push_back(a.get());
+    for (const auto &b : B) pb.push_back(b.get());
+    std::vector<Ciphertext> out;
+    std::vector<hec_ciphertext *> po;
+    out.reserve(p);
+    for (std::size_t i = 0; i < p; ++i) {
+        out.emplace_back(eval.context());
+        po.push_back(out.back().get());
+    }
+    check(hec_matmul_col_colT_bsgs(eval.context().get(), pa.data(), pa.size(), pb.data(), p, bs, form, rk.get(),
+                                   gk.get(), po.data()));
+    return out;
+}
 // The BSGS form of a matrix whose ciphertext diagonals arrive in natural form: diags[j] rotated right by
 // (j / bs_eff) bs_eff slots, one rotate_vector at a time.  Once per matrix; gk needs the negative giant steps (or
 // their NAF chains), and every rotation adds key-switch noise to its diagonal, which rolling the slot vectors before

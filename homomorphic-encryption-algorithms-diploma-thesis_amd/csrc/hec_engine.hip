@@ -29,6 +29,7 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <optional>
 #include <set>
 #include <thread>
@@ -1214,8 +1215,9 @@ std::vector<double> bsgs_check(hec_context *ctx, const hec_ciphertext *const *di
     return ps;
 }
 
-// The rotations of a BSGS call, shared by the ct x pt and the ct x ct form: the trie of rotate(x, i), i < bs, every
-// node with a buffer of its own (per[d] nodes at depth d), and giant g's key switches
+// The rotations of a BSGS call, shared by the matvec's two forms and the col x col^T product: the trie of
+// rotate(x, steps[t]) (terminal tag t; step 0 is x itself), every node with a buffer of its own (per[d] nodes at depth
+// d), and the key switches of the rotations by g bs, 1 <= g < G, that run after the inner sums
 struct BsgsRots {
     RotTrie trie;
     std::vector<std::vector<u32>> gelts;
@@ -1223,17 +1225,17 @@ struct BsgsRots {
     int D = 0;
     bool hoist = false;
 };
-BsgsRots bsgs_rots(const Ctx &c, const BsgsPlan &plan, const hec_galois_keys &gk)
+BsgsRots bsgs_rots(const Ctx &c, const std::vector<int> &steps, std::size_t bs, std::size_t G, const hec_galois_keys &gk)
 {
     BsgsRots r;
-    r.gelts.resize(plan.G);
+    r.gelts.resize(G);
     std::vector<u32> seq;
-    for (std::size_t i = 0; i < plan.bs; ++i) {
+    for (std::size_t t = 0; t < steps.size(); ++t) {
         seq.clear();
-        rotation_elts(c, (int)i, gk, seq);
-        r.trie.insert(seq, i);
+        rotation_elts(c, steps[t], gk, seq);
+        r.trie.insert(seq, t);
     }
-    for (std::size_t g = 1; g < plan.G; ++g) rotation_elts(c, (int)(g * plan.bs), gk, r.gelts[g]);
+    for (std::size_t g = 1; g < G; ++g) rotation_elts(c, (int)(g * bs), gk, r.gelts[g]);
     r.D = r.trie.depth;
     std::vector<int> depth_of(r.trie.nodes.size(), 0);
     r.per.assign((std::size_t)r.D + 1, 0);
@@ -1327,7 +1329,9 @@ void bsgs_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec_p
     const std::vector<double> ps = bsgs_check(ctx, diags, pdiags, n, plan, cols, p, rk, gk, out);
     const std::size_t l = cols[0]->level, N = c.N, bs = plan.bs, G = plan.G;
     const std::size_t GG = (std::size_t)bsgs_tile(c, !pt);
-    const BsgsRots rots = bsgs_rots(c, plan, *gk);
+    std::vector<int> babies(bs);
+    std::iota(babies.begin(), babies.end(), 0);
+    const BsgsRots rots = bsgs_rots(c, babies, bs, G, *gk);
     const int D = rots.D;
     const std::size_t nbuf = rots.trie.nodes.size();
     const u64 S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
@@ -1415,6 +1419,148 @@ void bsgs_core(hec_context *ctx, const hec_ciphertext *const *diags, const hec_p
         for (std::size_t i = 0; i < cnt; ++i) store_ct(c, out[b0 + i], O + i * So, 2, l - 1, ps[b0 + i] / ql);
     }
     HEC_HIP(hipStreamSynchronize(c.stream));  // the host pointer tables go out of scope
+}
+
+// ---------------------------------------------------------------- baby-step giant-step col x col^T product
+// BatchedMatrix::matmul's col x col^T branch (hec_matmul_col_colT) over the schedule above (opt-in, not
+// that entry's bits unless bs_eff = p).  With output i = g bs + b:
+//   Bb[j][b] = rotate_vector(B[j], b)         b < bs
+//   Ag[j][g] = rotate_vector(A[j], -g bs)     g < G
+//   acc_i    = sum_{j < n} multiply(Bb[j][b], Ag[j][g])                                     (size 3)
+//   r_i      = rescale_to_next(relinearize(acc_i))
+//   out[i]   = r_i (form HEC_DIAG_BSGS), rotate_vector(r_i, g bs) (form HEC_DIAG_NATURAL)
+// r_i is diagonal i rotated right by g bs slots, hec_matmul_diag_col_bsgs's input form for the same bs.
+struct CctPlan {
+    std::size_t bs = 0, G = 0;
+    std::vector<int> steps;  // babies, negative giants, (form 0) positive giants
+};
+CctPlan colcolt_plan(uint64_t p, uint64_t bs, int form)
+{
+    need(p >= 1, "empty matrix operand");
+    need(p < (1ull << 30), "step count too large");  // the steps are ints
+    need(form == HEC_DIAG_NATURAL || form == HEC_DIAG_BSGS, "form must be HEC_DIAG_NATURAL or HEC_DIAG_BSGS");
+    if (bs == 0)
+        for (bs = 1; bs * bs < p;) bs <<= 1;  // the smallest power of two >= sqrt(p), as bsgs_plan
+    CctPlan pl;
+    pl.bs = (std::size_t)std::min<uint64_t>(bs, p);
+    pl.G = (p + pl.bs - 1) / pl.bs;
+    for (std::size_t b = 1; b < pl.bs; ++b) pl.steps.push_back((int)b);
+    for (std::size_t g = 1; g < pl.G; ++g) pl.steps.push_back(-(int)(g * pl.bs));
+    if (form == HEC_DIAG_NATURAL)
+        for (std::size_t g = 1; g < pl.G; ++g) pl.steps.push_back((int)(g * pl.bs));
+    return pl;
+}
+
+void colcolt_bsgs(hec_context *ctx, const hec_ciphertext *const *A, std::size_t n, const hec_ciphertext *const *B,
+                  std::size_t p, uint64_t bs_arg, int form, const hec_kswitch_key *rk, const hec_galois_keys *gk,
+                  hec_ciphertext *const *out)
+{
+    Ctx &c = ctx->c;
+    need(A && B && out && n >= 1 && p >= 1, "null argument");
+    const CctPlan plan = colcolt_plan(p, bs_arg, form);
+    check_obj(ctx, gk, BAD_GK);
+    for (std::size_t j = 0; j < n; ++j) {
+        check_ct(ctx, A[j]);
+        check_ct(ctx, B[j]);
+    }
+    const std::size_t l = A[0]->level, N = c.N, bs = plan.bs, G = plan.G;
+    for (std::size_t j = 0; j < n; ++j) need(A[j]->size == 2 && B[j]->size == 2, "encrypted size must be 2");
+    for (std::size_t j = 0; j < n; ++j)
+        need(A[j]->level == l && B[j]->level == l, "encrypted1 and encrypted2 parameter mismatch");
+    double sc = 0;
+    for (std::size_t j = 0; j < n; ++j) {
+        const double s = B[j]->scale * A[j]->scale;
+        need(scale_ok(c, s, l), "scale out of bounds");
+        if (j == 0) sc = s;
+        else need(are_close(sc, s), "scale mismatch");
+    }
+    if (l < 2) throw std::invalid_argument("end of modulus switching chain reached");
+    check_obj(ctx, rk, BAD_RK);
+    {
+        std::vector<u32> seq;  // rotate_internal's own errors over every planned step
+        for (int st : plan.steps) {
+            seq.clear();
+            rotation_elts(c, st, *gk, seq);
+        }
+    }
+    check_out_alias({}, out, p, ctx, A, n);
+    check_out_alias({}, out, p, ctx, B, n);
+
+    std::vector<int> bsteps(bs), gsteps(G);
+    for (std::size_t b = 0; b < bs; ++b) bsteps[b] = (int)b;
+    for (std::size_t g = 0; g < G; ++g) gsteps[g] = -(int)(g * bs);
+    const BsgsRots rotsB = bsgs_rots(c, bsteps, bs, form == HEC_DIAG_NATURAL ? G : 1, *gk);  // with the output giants
+    const BsgsRots rotsA = bsgs_rots(c, gsteps, bs, 1, *gk);
+    const std::size_t nbuf = rotsB.trie.nodes.size() + rotsA.trie.nodes.size();
+    const int D = std::max(rotsB.D, rotsA.D);
+    const bool hoist = rotsB.hoist || rotsA.hoist;
+    const u64 S2 = 2 * l * N, S3 = 3 * l * N, So = 2 * (l - 1) * N;
+    // the tail (relinearise, rescale, form 0's giant rotations) runs over the outputs in groups of at most Pc
+    const std::size_t ymax = std::max<std::size_t>(1, 65535 / ((l + 1) * l));
+    const std::size_t Pc = std::min<std::size_t>({p, 256, ymax});
+    auto words_for = [&](std::size_t Jc) {
+        const std::size_t Bks = std::max(Jc, Pc);
+        std::size_t w = p * (S3 + So) + nbuf * Jc * S2 + 2 * Bks * l * N + ks_words(c, Bks, l) +
+                        rescale_words(c, Pc, 2, l) + bs + G + (nbuf + 200) * 64;
+        if (hoist) w += (std::size_t)D * hoist_words(c, Jc, l) + hoisted_child_words(c, Jc, l);
+        return w;
+    };
+    // columns per pass: k_colcolt_inner's exact FP64 sums (512), the y-blocks of the key switch's mod-up launch,
+    // option "cct_jchunk", and a workspace that fits the free device memory
+    std::size_t Jc = std::min<std::size_t>({n, 512, ymax});
+    if (c.cct_jchunk > 0) Jc = std::min<std::size_t>(Jc, (std::size_t)c.cct_jchunk);
+    if (words_for(Jc) > c.ws.words) {
+        std::size_t fr = 0, tot = 0;
+        HEC_HIP(hipMemGetInfo(&fr, &tot));
+        while (Jc > 1 && words_for(Jc) > c.ws.words && (double)words_for(Jc) * 8.0 > 0.9 * (double)fr) Jc = (Jc + 1) / 2;
+    }
+    Scratch s(c, words_for(Jc));
+    u64 *AC = s.take(p * S3), *O = s.take(p * So);
+    const u64 **tabB = reinterpret_cast<const u64 **>(s.take(bs));
+    const u64 **tabA = reinterpret_cast<const u64 **>(s.take(G));
+    std::vector<const u64 *> hrB(bs), hrA(G);
+    hec_galois_keys &gkm = const_cast<hec_galois_keys &>(*gk);  // the lazily built per-key tables are caches
+    bsgs_key_tables(ctx, rotsB, gkm, l);
+    bsgs_key_tables(ctx, rotsA, gkm, l);
+    const std::size_t mark = s.top;
+    for (std::size_t j0 = 0; j0 < n; j0 += Jc) {
+        const std::size_t cnt = std::min(Jc, n - j0);
+        s.top = mark;  // every carve of a pass is sized by its own count (the hoisted accumulators are contiguous)
+        TrieBufs bufsB(s, rotsB.per, cnt * S2), bufsA(s, rotsA.per, cnt * S2);
+        std::vector<Hoist> hs((std::size_t)D);
+        if (hoist)
+            for (int d = 0; d < D; ++d) hs[(std::size_t)d] = hoist_alloc(c, s, (int)cnt, (int)l);
+        bsgs_babies(ctx, s, rotsB, gkm, bufsB, hs, B + j0, cnt, l, hrB, tabB);  // every giant rotates the same source
+        bsgs_babies(ctx, s, rotsA, gkm, bufsA, hs, A + j0, cnt, l, hrA, tabA);
+        CctInner a{};
+        a.Bb = tabB; a.Ag = tabA; a.acc = AC; a.p = p; a.bs = (int)bs; a.G = (int)G;
+        u64 nbt, ngt;
+        colcolt_tiles(c, a, nbt, ngt);
+        ProfScope pr(c, "cct_inner");
+        // every baby buffer (2 cnt l) once per giant tile, every giant buffer once per baby tile, the accumulators
+        // written once and, when not assigning, read once
+        ProfScope k(c, "k:k_colcolt_inner", 2.0 * cnt * l * ((double)bs * (double)ngt + (double)G * (double)nbt) +
+                                                (j0 == 0 ? 1.0 : 2.0) * 3.0 * (double)p * l);
+        colcolt_inner(c, a, S2, l * N, S3, l * N, (int)cnt, (int)l, j0 == 0);
+    }
+    s.top = mark;
+    for (std::size_t i0 = 0; i0 < p; i0 += Pc) {
+        const std::size_t cnt = std::min(Pc, p - i0);
+        relin_rescale(c, s, AC + i0 * S3, rk->d, (int)cnt, (int)l, PolyArr{O + i0 * So, So, (l - 1) * N}, "cct_relin");
+    }
+    if (form == HEC_DIAG_NATURAL) {  // out[i] = rotate_vector(r_i, g bs): one batched chain per giant group
+        ProfScope pr(c, "cct_giants");
+        for (std::size_t g = 1; g < G; ++g) {
+            const std::size_t ng = std::min(bs, p - g * bs);
+            for (std::size_t i0 = 0; i0 < ng; i0 += Pc) {
+                const std::size_t cnt = std::min(Pc, ng - i0);
+                const PolyArr X{O + (g * bs + i0) * So, So, (l - 1) * N};
+                for (u32 e : rotsB.gelts[g]) galois_ks(c, s, X, X, (int)cnt, (int)(l - 1), e, gk->keys.at(e));
+            }
+        }
+    }
+    const double so = sc / (double)c.q[l - 1];
+    for (std::size_t i = 0; i < p; ++i) store_ct(c, out[i], O + i * So, 2, l - 1, so);
 }
 
 
@@ -2142,6 +2288,9 @@ int hec_context_set_option(hec_context *ctx, const char *name, int64_t value)
             else if (n == "bsgs_ct_bg") c.bsgs_ct_bg = one_of(BsgsCtBG{}, " takes 1 or 2");
             else if (n == "bsgs_ct_gg") c.bsgs_ct_gg = one_of(BsgsCtGG{}, " takes 2, 4 or 8");
             else if (n == "bsgs_order") c.bsgs_order = in(0, 1);
+            else if (n == "cct_jchunk") c.cct_jchunk = in(0, 512);
+            else if (n == "cct_tb") c.cct_tb = one_of(CctTB{}, " takes 1, 2 or 4");
+            else if (n == "cct_tg") c.cct_tg = one_of(CctTG{}, " takes 1, 2 or 4");
             else throw std::invalid_argument("unknown option");
         };
         HEC_HIP(hipStreamSynchronize(ctx->c.stream));
@@ -3756,6 +3905,28 @@ int hec_matmul_diag_col_bsgs(hec_context *ctx, const hec_ciphertext *const *diag
         set_device(ctx);
         need(diags && cols && out, "null argument");
         bsgs_core(ctx, diags, nullptr, n, bsgs_plan(n, bs), cols, p, rk, gk, out);
+    });
+}
+
+int hec_colcolT_bsgs_plan(uint64_t p, uint64_t bs, int form, int *steps, uint64_t cap, uint64_t *count,
+                          uint64_t *bs_eff)
+{
+    return guard([&] {
+        need(count != nullptr && (steps != nullptr || cap == 0), "null argument");
+        const CctPlan plan = colcolt_plan(p, bs, form);
+        *count = plan.steps.size();
+        if (bs_eff) *bs_eff = plan.bs;
+        for (std::size_t i = 0; i < plan.steps.size() && i < cap; ++i) steps[i] = plan.steps[i];
+    });
+}
+
+int hec_matmul_col_colT_bsgs(hec_context *ctx, const hec_ciphertext *const *A, uint64_t n,
+                             const hec_ciphertext *const *B, uint64_t p, uint64_t bs, int form,
+                             const hec_kswitch_key *rk, const hec_galois_keys *gk, hec_ciphertext *const *out)
+{
+    return guard([&] {
+        set_device(ctx);
+        colcolt_bsgs(ctx, A, n, B, p, bs, form, rk, gk, out);
     });
 }
 

@@ -159,6 +159,10 @@ struct Ctx {
                                    // consecutive block ids, 0 coefficient blocks consecutive.  Same words
     int bsgs_ct_bg = 2, bsgs_ct_gg = 8;  // options "bsgs_ct_bg", "bsgs_ct_gg": k_bsgs_inner_ct's tile (members of
                                    // BsgsCtBG, BsgsCtGG below).  Same words
+    int cct_jchunk = 0;            // option "cct_jchunk": columns per pass of hec_matmul_col_colT_bsgs, 0 automatic (at most
+                                   // 512: k_colcolt_inner's exact FP64 sums).  Same words
+    int cct_tb = 4, cct_tg = 2;    // options "cct_tb", "cct_tg": k_colcolt_inner's tile, babies x giants per thread
+                                   // (members of CctTB, CctTG below).  Same words
     bool debug_lanes = false;      // HEC_DEBUG_LANES=1 (debug): per call, report nodes with zero lists, the overflow
                                    // flag and changes of the per-key tables (stderr)
     // profiling (ProfScope in hec_engine.hip)
@@ -315,6 +319,22 @@ using BsgsCtBG = IntList<1, 2>;
 using BsgsCtGG = IntList<2, 4, 8>;
 int bsgs_tile(const Ctx &c, bool ct);  // giants per launch (option "bsgs_gg", ct: "bsgs_ct_gg")
 void bsgs_inner(Ctx &c, const BsgsInner &a, bool ct, u64 r_sb, u64 r_sk, u64 a_sk, u64 o_sb, u64 o_sk, int B, int l);
+// the inner sums of the baby-step giant-step col x col^T product (k_colcolt_inner) for a pass of J <= 512 columns:
+// acc[g bs + b] (=|+=) sum_{j < J} Bb[b][j] (x) Ag[g][j] for b < bs, g < G, g bs + b < p.  Bb (bs pointers) and Ag (G
+// pointers) are device tables of buffers that hold the pass's J size-2 ciphertexts sb apart, polys sk apart; acc holds
+// the p size-3 accumulators o_ss apart, polys o_sk apart.  The tile (TB babies x TG giants per thread) comes from the
+// options "cct_tb", "cct_tg" (members of CctTB, CctTG), the grid order from "bsgs_order"
+struct CctInner {
+    const u64 *const *Bb;
+    const u64 *const *Ag;
+    u64 *acc;
+    u64 p;
+    int bs, G;
+};
+using CctTB = IntList<1, 2, 4>;
+using CctTG = IntList<1, 2, 4>;
+void colcolt_tiles(const Ctx &c, const CctInner &a, u64 &nbt, u64 &ngt);  // the launch's baby and giant tiles
+void colcolt_inner(Ctx &c, const CctInner &a, u64 sb, u64 sk, u64 o_ss, u64 o_sk, int J, int l, bool assign);
 void tensor_sum(Ctx &c, PolyArr R, PolyArr A, u64 *ACC, u64 acc_sk, int B, int l);
 void ew_add(Ctx &c, PolyArr a, PolyArr b, PolyArr out, int B, int nk, int nl, int mode);  // 0 add, 1 sub
 void ew_negate(Ctx &c, PolyArr a, int B, int nk, int nl);

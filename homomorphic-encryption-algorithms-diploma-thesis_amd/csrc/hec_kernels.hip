@@ -4169,6 +4169,162 @@ void bsgs_inner(Ctx &c, const BsgsInner &a, bool ct, u64 r_sb, u64 r_sk, u64 a_s
     HEC_HIP(hipGetLastError());
 }
 
+// The inner sums of the baby-step giant-step col x col^T product (hec_engine.hip colcolt_bsgs) for one pass of J
+// columns: the size-3 tensor products of the baby rotations Bb[b] = rotate(B[j], b) with the giant rotations
+// Ag[g] = rotate(A[j], -g bs), summed over the pass's columns j,
+//   ACC_i[0] (=|+=) sum_j Bb[b][j][0] Ag[g][j][0]
+//   ACC_i[1] (=|+=) sum_j (Bb[b][j][0] Ag[g][j][1] + Bb[b][j][1] Ag[g][j][0])
+//   ACC_i[2] (=|+=) sum_j Bb[b][j][1] Ag[g][j][1]                     i = g bs + b < p,  mod q
+// A thread owns one coefficient of one limb for a tile of TB babies x TG giants: per column it loads the 2 TB baby
+// words and the 2 TG giant words once, forms the TB TG products and keeps 3 TB TG accumulators, so a launch reads every
+// baby buffer ceil(G / TG) times and every giant buffer ceil(bs / TB) times.  The arithmetic is k_bsgs_inner_ct's, and
+// so k_tensor_multi2<false>'s: 60-bit primes reduce d0 and d2 per product (mulmod), form d1 from the 128-bit sum of its
+// two products (mac128, barrett128) and add mod q; FP64 primes sum exact fp_mulmod products as integer-valued doubles
+// and canonicalise once per launch.  Every multiply's words are thus reduced as SEAL reduces them and the sums are
+// exact, so the words equal the per-operation composition's.
+// The FP64 bound is k_bsgs_inner_ct's: fp_canon takes |x| < 2^52 (hec_device.h); a product is at most 0.53 q in
+// magnitude and the middle accumulator adds two per column, so |s1| <= 1.06 q J, which with q < 2^42 (the FP class)
+// is below 2^52 for J <= floor(2^10 / 1.06) = 966.  colcolt_inner() therefore refuses J > 512, and the engine cuts the
+// sum over j into passes of at most 512 columns.
+// Across passes: assign stores the canonical sums; otherwise the thread reads the stored canonical word and adds mod q.
+// Each (idx, i) word belongs to one thread of one block, so there is no race.  Babies b >= bs, giants g >= G and
+// outputs i >= p (the partial last giant group) are masked: their operands are not loaded and nothing is stored.
+// The baby and giant pointers (bs + G separate buffers of J ciphertexts, sb apart) come from device tables.
+// order 1: the TB x TG tiles of one coefficient block take consecutive block ids (baby tiles fastest), so the blocks
+// resident together read the same 256 coefficients of all bs + G operands and every operand word comes from HBM once
+// and from L2 / MALL for the other tiles that share its row or column; sharing both operand sets at once is the point
+// of this order, since neither set is small (bs ~ G).  order 0: coefficient blocks consecutive (the plain grid).
+template <int TB, int TG>
+__global__ void __launch_bounds__(256)
+    k_colcolt_inner(CctInner a, u64 sb, u64 sk, u64 o_ss, u64 o_sk, int J, int logN, u64 total,
+                    const DevPrime *__restrict__ primes, int nbt, int ncb, int ntile, int order, int assign)
+{
+    const u32 id = blockIdx.x;
+    const int cb = order ? (int)(id / (u32)ntile) : (int)(id % (u32)ncb);
+    const int tile = order ? (int)(id % (u32)ntile) : (int)(id / (u32)ncb);
+    const u64 idx = (u64)cb * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int b0 = (tile % nbt) * TB, g0 = (tile / nbt) * TG;
+    if (b0 >= a.bs || g0 >= a.G) return;
+    const DevPrime pr = primes[idx >> logN];
+    const u64 *pb[TB], *pg[TG];
+#pragma unroll
+    for (int b = 0; b < TB; ++b) pb[b] = b0 + b < a.bs ? a.Bb[b0 + b] + idx : nullptr;
+#pragma unroll
+    for (int g = 0; g < TG; ++g) pg[g] = g0 + g < a.G ? a.Ag[g0 + g] + idx : nullptr;
+    u64 d0[TG][TB], d1[TG][TB], d2[TG][TB];
+    if (pr.fp) {
+        double s0[TG][TB], s1[TG][TB], s2[TG][TB];
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int b = 0; b < TB; ++b) s0[g][b] = s1[g][b] = s2[g][b] = 0;
+        u64 off = 0;
+        for (int j = 0; j < J; ++j, off += sb) {
+            double x0[TB], x1[TB], y0[TG], y1[TG];
+#pragma unroll
+            for (int b = 0; b < TB; ++b) {
+                x0[b] = pb[b] ? u2d(pb[b][off]) : 0.0;
+                x1[b] = pb[b] ? u2d(pb[b][off + sk]) : 0.0;
+            }
+#pragma unroll
+            for (int g = 0; g < TG; ++g) {
+                y0[g] = pg[g] ? u2d(pg[g][off]) : 0.0;
+                y1[g] = pg[g] ? u2d(pg[g][off + sk]) : 0.0;
+            }
+#pragma unroll
+            for (int g = 0; g < TG; ++g)
+#pragma unroll
+                for (int b = 0; b < TB; ++b) {
+                    s0[g][b] += fp_mulmod(x0[b], y0[g], pr.qd, pr.qinv);
+                    s1[g][b] += fp_mulmod(x0[b], y1[g], pr.qd, pr.qinv) + fp_mulmod(x1[b], y0[g], pr.qd, pr.qinv);
+                    s2[g][b] += fp_mulmod(x1[b], y1[g], pr.qd, pr.qinv);
+                }
+        }
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int b = 0; b < TB; ++b) {
+                d0[g][b] = fp_canon(s0[g][b], pr.qd, pr.qinv);
+                d1[g][b] = fp_canon(s1[g][b], pr.qd, pr.qinv);
+                d2[g][b] = fp_canon(s2[g][b], pr.qd, pr.qinv);
+            }
+    } else {
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int b = 0; b < TB; ++b) d0[g][b] = d1[g][b] = d2[g][b] = 0;
+        u64 off = 0;
+        for (int j = 0; j < J; ++j, off += sb) {
+            u64 x0[TB], x1[TB], y0[TG], y1[TG];
+#pragma unroll
+            for (int b = 0; b < TB; ++b) {
+                x0[b] = pb[b] ? pb[b][off] : 0;
+                x1[b] = pb[b] ? pb[b][off + sk] : 0;
+            }
+#pragma unroll
+            for (int g = 0; g < TG; ++g) {
+                y0[g] = pg[g] ? pg[g][off] : 0;
+                y1[g] = pg[g] ? pg[g][off + sk] : 0;
+            }
+#pragma unroll
+            for (int g = 0; g < TG; ++g)
+#pragma unroll
+                for (int b = 0; b < TB; ++b) {
+                    d0[g][b] = addmod(d0[g][b], mulmod(x0[b], y0[g], pr), pr.q);
+                    U128 m{x0[b] * y1[g], mulhi64(x0[b], y1[g])};
+                    mac128(m, x1[b], y0[g]);
+                    d1[g][b] = addmod(d1[g][b], barrett128(m.lo, m.hi, pr.q, pr.r0, pr.r1), pr.q);
+                    d2[g][b] = addmod(d2[g][b], mulmod(x1[b], y1[g], pr), pr.q);
+                }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < TG; ++g)
+#pragma unroll
+        for (int b = 0; b < TB; ++b) {
+            const u64 i = (u64)(g0 + g) * (u64)a.bs + (u64)(b0 + b);
+            if (b0 + b >= a.bs || g0 + g >= a.G || i >= a.p) continue;
+            u64 *o = a.acc + i * o_ss + idx;
+            if (assign) {
+                o[0] = d0[g][b];
+                o[o_sk] = d1[g][b];
+                o[2 * o_sk] = d2[g][b];
+            } else {
+                o[0] = addmod(o[0], d0[g][b], pr.q);
+                o[o_sk] = addmod(o[o_sk], d1[g][b], pr.q);
+                o[2 * o_sk] = addmod(o[2 * o_sk], d2[g][b], pr.q);
+            }
+        }
+}
+
+void colcolt_tiles(const Ctx &c, const CctInner &a, u64 &nbt, u64 &ngt)
+{
+    nbt = ((u64)a.bs + (u64)c.cct_tb - 1) / (u64)c.cct_tb;
+    ngt = ((u64)a.G + (u64)c.cct_tg - 1) / (u64)c.cct_tg;
+}
+
+void colcolt_inner(Ctx &c, const CctInner &a, u64 sb, u64 sk, u64 o_ss, u64 o_sk, int J, int l, bool assign)
+{
+    // J <= 512: the exact FP64 sums (k_colcolt_inner).  The outputs lie inside the p accumulators: (G - 1) bs < p
+    if (J < 1 || J > 512 || a.bs < 1 || a.G < 1 || a.p < 1 || (u64)(a.G - 1) * (u64)a.bs >= a.p)
+        throw std::logic_error("colcolt_inner: bad pass");
+    const u64 total = (u64)l * c.N;
+    const u64 ncb = (total + 255) / 256;
+    u64 nbt, ngt;
+    colcolt_tiles(c, a, nbt, ngt);
+    const u64 blocks = ncb * nbt * ngt;
+    if (blocks >= (1ull << 31)) throw std::logic_error("colcolt_inner: grid too large");
+    const dim3 grid((unsigned)blocks);
+    const bool found = bsgs_dispatch(CctTB{}, CctTG{}, c.cct_tb, c.cct_tg, [&](auto tb, auto tg) {
+        k_colcolt_inner<decltype(tb)::value, decltype(tg)::value><<<grid, 256, 0, c.stream>>>(
+            a, sb, sk, o_ss, o_sk, J, c.logN, total, c.primes, (int)nbt, (int)ncb, (int)(nbt * ngt), c.bsgs_order,
+            assign ? 1 : 0);
+    });
+    if (!found) throw std::logic_error("colcolt_inner: no kernel for this tile");
+    HEC_HIP(hipGetLastError());
+}
+
 // ACC (size 3) = sum_b R[b] (x) A[b]  (col x col^T form: one output, the batch is the j-sum)
 __global__ void __launch_bounds__(256)
     k_tensor_sum(PolyArr R, PolyArr A, u64 *__restrict__ ACC, u64 acc_sk, int B, int logN, u64 total,

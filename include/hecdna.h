@@ -352,6 +352,51 @@ int hec_matmul_finish(hec_context *ctx, hec_ciphertext *const *acc, uint64_t p, 
 int hec_matmul_col_colT(hec_context *ctx, const hec_ciphertext *const *A, uint64_t n,
                         const hec_ciphertext *const *B, uint64_t p, const hec_kswitch_key *rk,
                         const hec_galois_keys *gk, hec_ciphertext *const *out);
+/* The form of a matrix's ciphertext diagonals: natural (diagonal i as it is), or the BSGS form for a block size bs
+ * (diagonal i rotated right by (i / bs_eff) bs_eff slots, what hec_matmul_diag_col_bsgs takes). */
+#define HEC_DIAG_NATURAL 0
+#define HEC_DIAG_BSGS 1
+/* The rotation steps of hec_matmul_col_colT_bsgs below (host only, no context), with bs_eff = min(bs, p), G =
+ * ceil(p / bs_eff) and bs = 0 the smallest power of two >= sqrt(p) (hec_bsgs_plan's rule applied to p): the babies
+ * 1 .. bs_eff - 1, then the negative giants -g bs_eff for 1 <= g < G, then, for form HEC_DIAG_NATURAL only, the
+ * positive giants g bs_eff for 1 <= g < G.  A key set with exactly these steps' elements makes every rotation one
+ * key switch.  *count = the number of steps, min(cap, *count) of them written to steps; *bs_eff (optional) = bs_eff.
+ * HEC_EINVAL for p = 0, p >= 2^30 and a form outside {0, 1}. */
+int hec_colcolT_bsgs_plan(uint64_t p, uint64_t bs, int form, int *steps, uint64_t cap, uint64_t *count,
+                          uint64_t *bs_eff);
+/* col x col^T -> diag product on the baby-step giant-step schedule: the product of hec_matmul_col_colT from
+ * n (bs_eff - 1) baby rotations of B and n (G - 1) giant rotations of A in place of its n (p - 1) rotations of B.
+ * With output i = g bs_eff + b (b < bs_eff, g < G, i < p):
+ *   Bb[j][b] = rotate_vector(B[j], b)               (b = 0: B[j] itself)
+ *   Ag[j][g] = rotate_vector(A[j], -g bs_eff)       (g = 0: A[j] itself)
+ *   acc_i    = sum_{j < n} multiply(Bb[j][b], Ag[j][g])                                        (size 3)
+ *   r_i      = rescale_to_next(relinearize(acc_i, rk))
+ *   out[i]   = r_i                                  form HEC_DIAG_BSGS
+ *   out[i]   = rotate_vector(r_i, g bs_eff)         form HEC_DIAG_NATURAL (g = 0: r_i)
+ * since rot(B[j], i) (.) A[j] = rot( rot(B[j], b) (.) rot(A[j], -g bs_eff), g bs_eff ).  The result IS word for word,
+ * with level and scale, what the per-operation calls above give when composed in this order, rotate_vector by SEAL's
+ * rule (the step's own key, else its NAF chain).  It is NOT the bits of hec_matmul_col_colT unless G = 1 (bs_eff = p),
+ * where the two definitions coincide and both forms are equal (it decrypts to the same product).  Form HEC_DIAG_BSGS
+ * with block size bs is the input form of hec_matmul_diag_col_bsgs with the same bs and n = p: r_i is diagonal i
+ * rotated right by g bs_eff slots, so the output needs no rotation at all and feeds that matvec directly (no
+ * bsgs_rotate_diagonals pass).  Outputs have level l - 1 and scale sc / q_{l-1}, sc = B[j]->scale A[j]->scale.
+ * Every check comes before the first write, in this order: null arguments and n, p >= 1; the form; the Galois keys
+ * of this context; every A[j] and B[j] (object, size 2, one level); "scale out of bounds" and "scale mismatch" over
+ * B[j]->scale A[j]->scale; "end of modulus switching chain reached" for l < 2; rk of this context; "Galois key not
+ * present" over every step of hec_colcolT_bsgs_plan (a key holds every level, so one found at level l serves the
+ * positive giants at l - 1 too); the aliasing rule: an output handle that is any input, or that is listed twice, is
+ * HEC_EINVAL.  Nothing is written on an error.
+ * Runs on the context's stream in passes of Jc columns: Jc <= 512 (the inner-sum kernel adds two exact FP64 products
+ * per column, which stays below 2^52 for 966 columns at most), Jc <= 65,535 / ((l + 1) l), at most
+ * "cct_jchunk" (option, 0..512, 0 = automatic).  The workspace holds the p size-3 accumulators, the p outputs,
+ * (nodes_B + nodes_A + 2) Jc ciphertexts for the two rotation tries (their nodes beside the roots: bs_eff - 1 and
+ * G - 1 with a key per step, more on a sparser key set) and the key switch's own; Jc is halved until that fits the
+ * free device memory, and when not even one column fits the call fails with HEC_EDEVICE.  The outputs do not depend
+ * on the pass size, nor on "cct_tb" (1, 2, 4), "cct_tg" (1, 2, 4) and "bsgs_order" (0..1), the inner-sum kernel's
+ * tile and grid order.  Batch lanes and the sharded path do not take this route. */
+int hec_matmul_col_colT_bsgs(hec_context *ctx, const hec_ciphertext *const *A, uint64_t n,
+                             const hec_ciphertext *const *B, uint64_t p, uint64_t bs, int form,
+                             const hec_kswitch_key *rk, const hec_galois_keys *gk, hec_ciphertext *const *out);
 /* Matrix::matmul (he_linalg.cpp:202-236): column-major element-wise ciphertext matrices
  * (index i + rows*j, swapped when *_transposed); out has r1*c2 entries, column-major. */
 int hec_matrix_matmul(hec_context *ctx, const hec_ciphertext *const *A, uint64_t a_rows, uint64_t a_cols,
