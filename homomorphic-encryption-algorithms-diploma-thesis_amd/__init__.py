@@ -180,6 +180,9 @@ def lib():
             "hec_math_inv_sqrt_twice": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
             "hec_math_sqrt": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
             "hec_math_abs": [vp, vp, C.c_uint64, C.c_double, C.c_uint64, vp, vp],
+            "hec_math_poly_plan": [u64p, C.c_uint64, C.POINTER(C.c_double), C.c_uint64, C.c_uint64, C.c_uint64,
+                                   C.c_double, u64p, C.POINTER(C.c_double), u64p, u64p, u64p],
+            "hec_math_poly": [vp, vp, C.c_uint64, C.POINTER(C.c_double), C.c_uint64, C.c_uint64, vp, vp],
             "hec_drop_chain_levels": [vp, vp, C.c_uint64, C.c_uint64],
             "hec_multiply_relin_rescale_many": [vp, vp, vp, C.c_uint64, vp, vp],
             "hec_sum_elems_many": [vp, vp, C.c_uint64, C.c_uint64, vp, vp],
@@ -489,6 +492,22 @@ def math_plan(moduli, fn, a, iters, level, scale):
     _check(lib().hec_math_plan(_p(m), len(m), int(fn), float(a), int(iters), int(level), float(scale), C.byref(lv),
                                C.byref(sc)))
     return lv.value, sc.value
+
+
+def math_poly_plan(moduli, coeffs, level, scale, bs=None):
+    """hec_math_poly_plan (host only): (level, scale, bs, products, leaves) of Context.poly for inputs at (level,
+    scale) on the key moduli `moduli`: the result's level and scale, the block size used, the relinearised products
+    (powers included) and the linear-combination stages; raises InvalidArgument with the message of the first check
+    the schedule would fail."""
+    m = np.array([int(x) for x in moduli], dtype=np.uint64)
+    cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).ravel())
+    if cf.size < 1:
+        raise InvalidArgument(1, "polynomial must not be constant")
+    lv, sc, be, pr, le = C.c_uint64(), C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(lib().hec_math_poly_plan(_p(m), len(m), cf.ctypes.data_as(C.POINTER(C.c_double)), cf.size - 1,
+                                    int(bs or 0), int(level), float(scale), C.byref(lv), C.byref(sc), C.byref(be),
+                                    C.byref(pr), C.byref(le)))
+    return lv.value, sc.value, be.value, pr.value, le.value
 
 
 def sum_elems_plan(dim, cap=None):
@@ -937,6 +956,22 @@ class Context:
     def abs(self, cts, a, iters, rk, out=None):
         """hec_math_abs: he::math::abs."""
         return self._math(lib().hec_math_abs, cts, a, iters, rk, out)
+
+    def poly(self, cts, coeffs, rk, bs=None, out=None):
+        """hec_math_poly: sum_j coeffs[j] x^j on every ciphertext of the list (or on one, then one is returned) by
+        Paterson-Stockmeyer with block size bs (None: chosen from the degree).  The result keeps the input's scale."""
+        single = isinstance(cts, Ciphertext)
+        cts = [cts] if single else list(cts)
+        if out is None:
+            out = [Ciphertext(self) for _ in cts]
+        elif isinstance(out, Ciphertext):
+            out = [out]
+        cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).ravel())
+        if cf.size < 1:
+            raise InvalidArgument(1, "polynomial must not be constant")
+        _check(lib().hec_math_poly(self.h, self._arr(cts), len(cts), cf.ctypes.data_as(C.POINTER(C.c_double)),
+                                   cf.size - 1, int(bs or 0), rk.h, self._arr(out)))
+        return out[0] if single else out
 
     def drop_chain_levels(self, cts, levels):
         """hec_drop_chain_levels: he::util::drop_chain_levels on the ciphertext(s), in place."""

@@ -21,6 +21,9 @@
 //          mathb:<iter>   (the same four functions through he_math.h's vector overloads, each on all n input
 //                          ciphertexts as one batch: signed_inv(., 1.0), inv_sqrt_twice(., 0.7), sqrt(., 1.0),
 //                          abs(., 1.0); 4 n outputs in that order)
+//          polyb:<degree> (he::math::poly, he_math.h: the polynomial of coefficients c_j = (((7 j + 3) mod 11) - 5) / 8,
+//                          j = 0 .. degree (a zero leading coefficient becomes 1/2), on c0 alone and then on all n
+//                          input ciphertexts as one batch; 1 + n outputs in that order)
 //          linalgb:<dim>  (the he_linalg.h members that are one batched engine call: with M the BatchedMatrix of the n input
 //                          ciphertexts as vectors of dimension <dim>, eval % rk % M * M, M.square, M.sum_bvec_elems, then
 //                          eval % rk % A * A for the inputs as a 1 x n Matrix; 4 n outputs in that order)
@@ -234,7 +237,7 @@ int selfcontained(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
     if (argc != 4) {
-        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|linalgb:<dim>|math:<iter>|mathb:<iter>|"
+        std::cout << "usage: he_demo <batched_diag|batched_col|ops|matrix|matrix_family|encode|sum_elems:<dim>|linalgb:<dim>|math:<iter>|mathb:<iter>|polyb:<degree>|"
                      "util|least_squares|fft:<n>[:inv]|bfft:<n>[:inv]|decrypt|selfcontained|server> <in.bin> <out.bin>\n";
         return 1;
     }
@@ -382,6 +385,15 @@ int main(int argc, char **argv)
         for (auto &c : he::math::inv_sqrt_twice(cencd, eval, rk, cts, 0.7, iter)) keep.push_back(std::move(c));
         for (auto &c : he::math::sqrt(ctx, cencd, eval, rk, cts, 1.0, iter)) keep.push_back(std::move(c));
         for (auto &c : he::math::abs(ctx, cencd, eval, rk, cts, 1.0, iter)) keep.push_back(std::move(c));
+    } else if (mode.rfind("polyb:", 0) == 0) {
+        // he::math::poly (an extension over the reference): one ciphertext, then every input ciphertext in one batch
+        const std::size_t degree = std::stoul(mode.substr(6));
+        std::vector<double> coeffs(degree + 1);
+        for (std::size_t j = 0; j <= degree; ++j) coeffs[j] = ((double)((7 * j + 3) % 11) - 5.0) / 8.0;
+        if (coeffs[degree] == 0.0) coeffs[degree] = 0.5;
+        hecdna::CKKSEncoder cencd(ctx);
+        keep.push_back(he::math::poly(cencd, eval, rk, cts[0], coeffs));
+        for (auto &c : he::math::poly(cencd, eval, rk, cts, coeffs)) keep.push_back(std::move(c));
     } else if (mode.rfind("fft:", 0) == 0 || mode.rfind("bfft:", 0) == 0) {
         const bool slot = mode[0] == 'b';
         const std::string arg = mode.substr(slot ? 5 : 4);

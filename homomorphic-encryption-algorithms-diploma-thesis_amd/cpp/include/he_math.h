@@ -5,6 +5,7 @@
 // so on the same inputs and keys every intermediate ciphertext equals SEAL's bit for bit.
 #include <cstddef>
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "he_operators.h"
@@ -27,6 +28,13 @@ namespace he::math
     // f(x) = |x| (he_math.h:30-33)
     hecdna::Ciphertext abs(const hecdna::Context &ctx, const hecdna::CKKSEncoder &cencd, const hecdna::Evaluator &eval,
                            const hecdna::RelinKeys &rk, const hecdna::Ciphertext &x_ct, double a, std::size_t iter_num);
+
+    // An extension (the reference has no such function): f(x) = sum_j coeffs[j] x^j by Paterson-Stockmeyer with
+    // block size bs (a power of two in [2, 16]; 0: chosen from the degree), one engine call (hec_math_poly,
+    // include/hecdna.h; the schedule is DESIGN.md 2.9).  The result keeps x_ct's scale.  Real coefficients; the
+    // polynomial must not be constant
+    hecdna::Ciphertext poly(const hecdna::CKKSEncoder &cencd, const hecdna::Evaluator &eval, const hecdna::RelinKeys &rk,
+                            const hecdna::Ciphertext &x_ct, const std::vector<double> &coeffs, std::size_t bs = 0);
 
     // An extension (the reference has no such overloads): the same four functions on a vector of ciphertexts of one
     // level and scale, each one engine call (hec_math_*, include/hecdna.h) that runs every stage of the schedule
@@ -53,6 +61,26 @@ namespace he::math
             return res;
         }
     } // namespace detail
+
+    // poly on a vector of ciphertexts of one level and scale: one engine call over the whole batch
+    inline std::vector<hecdna::Ciphertext> poly(const hecdna::CKKSEncoder &, const hecdna::Evaluator &eval,
+                                                const hecdna::RelinKeys &rk, const std::vector<hecdna::Ciphertext> &x_cts,
+                                                const std::vector<double> &coeffs, std::size_t bs = 0)
+    {
+        const hecdna::Context &ctx = eval.context();
+        std::vector<hecdna::Ciphertext> res(x_cts.size());
+        std::vector<const hec_ciphertext *> in(x_cts.size());
+        std::vector<hec_ciphertext *> out(x_cts.size());
+        for (std::size_t i = 0; i < x_cts.size(); ++i) {
+            res[i].bind(ctx);
+            in[i] = x_cts[i].get();
+            out[i] = res[i].get();
+        }
+        if (coeffs.empty()) throw std::invalid_argument("polynomial must not be constant");
+        hecdna::check(hec_math_poly(ctx.get(), in.data(), in.size(), coeffs.data(), coeffs.size() - 1, bs, rk.get(),
+                                    out.data()));
+        return res;
+    }
 
     inline std::vector<hecdna::Ciphertext> signed_inv(const hecdna::CKKSEncoder &, const hecdna::Evaluator &eval,
                                                       const hecdna::RelinKeys &rk,

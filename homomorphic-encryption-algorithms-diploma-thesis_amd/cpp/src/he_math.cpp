@@ -9,6 +9,7 @@
 #include "he_math.h"
 
 #include <cassert>
+#include <stdexcept>
 
 using hecdna::Ciphertext;
 using hecdna::CKKSEncoder;
@@ -60,5 +61,19 @@ namespace he::math
                    const Ciphertext &x_ct, double a, std::size_t iter_num)
     {
         return run_one(hec_math_abs, eval, rk, x_ct, a, iter_num);
+    }
+
+    // sum_j coeffs[j] x^j, Paterson-Stockmeyer (an extension; include/hecdna.h hec_math_poly)
+    Ciphertext poly(const CKKSEncoder &, const Evaluator &eval, const RelinKeys &rk, const Ciphertext &x_ct,
+                    const std::vector<double> &coeffs, std::size_t bs)
+    {
+        const hecdna::Context &ctx = eval.context();
+        Ciphertext res;
+        res.bind(ctx);
+        const hec_ciphertext *in = x_ct.get();
+        hec_ciphertext *out = res.get();
+        if (coeffs.empty()) throw std::invalid_argument("polynomial must not be constant");
+        hecdna::check(hec_math_poly(ctx.get(), &in, 1, coeffs.data(), coeffs.size() - 1, bs, rk.get(), &out));
+        return res;
     }
 } // namespace he::math

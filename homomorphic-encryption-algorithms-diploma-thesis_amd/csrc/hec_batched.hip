@@ -322,6 +322,10 @@ int hec_bfft(hec_context *ctx, const hec_ciphertext *const *in, uint64_t B, uint
 // Two stage kinds (hec_kernels.hip): the scalar stage OUT = rescale(A (*) c) +- d (math_lastprod, the batched INTT,
 // fft_round_limbs, math_cstage) and the product stage OUT = rescale(relin(A (*) (B' + d))) (math_tensor, then
 // keyswitch and rescale_batch as hec_matmul_finish runs them).  The iterates live in slots of one Scratch workspace.
+// hec_math_poly (an extension: Paterson-Stockmeyer evaluation of a real polynomial) walks the same way
+// over MathRun::poly and adds a third stage kind, the linear combination OUT = rescale(sum_t A_t (*) c_t) + d of up to
+// HEC_MATH_MAXT values (math_lincomb_last, the same INTT and rounding limbs, math_lincomb), and views: a value read
+// below the level its slot was written at (MathRun::down), which is what mod_switch_to_next costs here.
 namespace {
 // The product stage over B ciphertexts at level l: OUT = rescale(relin(A (*) (Bp [+ dw]))) at level l - 1.  A and Bp
 // may be one array (the squares); T3: 3 B l N words for the size-3 products.  he::math's products and
@@ -341,6 +345,8 @@ struct MathVal {
     int slot = -1;
     std::size_t level = 0;
     double scale = 0;
+    std::size_t alloc = 0;  // limbs per poly of the slot's layout when it is read below the level it was written at
+                            // (a view, MathRun::down); 0: level
 };
 
 struct MathRun {
@@ -355,6 +361,16 @@ struct MathRun {
     // slot bookkeeping, the same on both walks
     std::vector<char> busy;
     int peak = 0;
+    // poly(): block size, the powers computed so far with the uses each still has, the counts hec_math_poly_plan
+    // reports, and every leaf's table in the order of the walk: its coefficient words, then three words per source
+    // (offset from slot 0, entry stride, poly stride), as math_lincomb reads them.  tab_dev: the plan's table on the
+    // device; slot_words: the distance of two slots (they are carved back to back); ring: N, 0 on a host-only plan
+    std::size_t bs = 0, nprod = 0, nleaf = 0, slot_words = 0, ring = 0;
+    MathVal x1;
+    std::map<std::size_t, MathVal> pw;
+    std::map<std::size_t, int> uses;
+    std::vector<u64> tab;
+    const u64 *tab_dev = nullptr;
 
     int take()
     {
@@ -372,12 +388,24 @@ struct MathRun {
     }
     PolyArr arr(const MathVal &v) const
     {
-        return PolyArr{slot[(std::size_t)v.slot], 2 * v.level * c->N, v.level * c->N};
+        const std::size_t al = v.alloc ? v.alloc : v.level;
+        return PolyArr{slot[(std::size_t)v.slot], 2 * al * c->N, al * c->N};
+    }
+    // mod_switch_to_next down to `level`: the same slot read at fewer limbs.  No copy and no launch; the checks are
+    // mod_switch_to_next's, one per level
+    MathVal down(const MathVal &v, std::size_t level) const
+    {
+        MathVal r = v;
+        r.alloc = v.alloc ? v.alloc : v.level;
+        for (std::size_t l = v.level; l > level; --l) need(ch.scale_ok(v.scale, l - 1), "scale out of bounds");
+        r.level = std::min(v.level, level);
+        return r;
     }
 
     // rescale(a (*) encode(cval, a.level, pscale)) [+- encode(dval) at the result's level and scale]: multiply_plain,
-    // rescale_to_next, add_plain / sub_plain.  dmode 0 none, 1 add, 2 subtract; pscale 0: a's own scale
-    MathVal cstage(const MathVal &a, double cval, int dmode = 0, double dval = 0, double pscale = 0)
+    // rescale_to_next, add_plain / sub_plain.  dmode 0 none, 1 add, 2 subtract; pscale 0: a's own scale; oscale
+    // non-zero: the result's scale is assigned ("scale := oscale") before d is encoded
+    MathVal cstage(const MathVal &a, double cval, int dmode = 0, double dval = 0, double pscale = 0, double oscale = 0)
     {
         const std::size_t l = a.level;
         u64 cw[HEC_MAXL + 1], dw[HEC_MAXL + 1];
@@ -388,7 +416,7 @@ struct MathRun {
         if (l == 1) throw std::invalid_argument("end of modulus switching chain reached");
         MathVal o;
         o.level = l - 1;
-        o.scale = ns / (double)ch.q[l - 1];
+        o.scale = oscale != 0 ? oscale : ns / (double)ch.q[l - 1];
         if (dmode) {
             scalar_words_chain(ch, dval, o.scale, o.level, dw);
             need(are_close(o.scale, o.scale), "scale mismatch");  // add_plain's check; the plaintext has o's scale
@@ -397,8 +425,9 @@ struct MathRun {
         }
         o.slot = take();
         if (c) {
-            const u64 N = c->N, sb = 2 * l * N, sk = l * N;
-            const u64 *A = slot[(std::size_t)a.slot];
+            const PolyArr pa = arr(a);
+            const u64 sb = pa.sb, sk = pa.sk;
+            const u64 *A = pa.p;
             {
                 ProfScope k(*c, "k:k_math_lastprod/math", 4.0 * B);
                 math_lastprod(*c, A, sb, sk, Y, B, 2, (int)l, cw[l - 1]);
@@ -440,6 +469,212 @@ struct MathRun {
         need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
         need(are_close(a.scale, b.scale), "scale mismatch");
         if (c) ew_add(*c, arr(a), arr(b), arr(a), B, 2, (int)a.level, 1);
+    }
+
+    // a + b into a's slot (add_inplace)
+    void add(MathVal &a, const MathVal &b)
+    {
+        need(a.level == b.level, "encrypted1 and encrypted2 parameter mismatch");
+        need(are_close(a.scale, b.scale), "scale mismatch");
+        if (c) ew_add(*c, arr(a), arr(b), arr(a), B, 2, (int)a.level, 0);
+    }
+
+    // a + encode(dval, a.level, a.scale) into a's slot (add_plain_inplace of a scalar)
+    void add_const(MathVal &a, double dval)
+    {
+        u64 dw[HEC_MAXL + 1];
+        scalar_words_chain(ch, dval, a.scale, a.level, dw);
+        need(are_close(a.scale, a.scale), "scale mismatch");
+        if (c) {
+            ProfScope k(*c, "k:k_math_addconst/math", 2.0 * B * a.level);
+            math_addconst(*c, arr(a), dw, B, (int)a.level);
+        }
+    }
+
+    // ------------------------------------------------------------ poly: Paterson-Stockmeyer
+    static std::size_t clog2(std::size_t j) { return j <= 1 ? 0 : 64 - (std::size_t)__builtin_clzll(j - 1); }
+    using Coeffs = std::vector<double>;
+    static void trim(Coeffs &p)
+    {
+        while (p.size() > 1 && p.back() == 0.0) p.pop_back();
+    }
+    static bool above0(const Coeffs &p)  // a non-zero coefficient above index 0
+    {
+        for (std::size_t j = 1; j < p.size(); ++j)
+            if (p[j] != 0.0) return true;
+        return false;
+    }
+    // g = bs 2^k, k the largest with g <= degree
+    std::size_t split_at(const Coeffs &p) const
+    {
+        std::size_t g = bs;
+        while (2 * g <= p.size() - 1) g *= 2;
+        return g;
+    }
+    // the level a sub-polynomial's value can be had at (may go below 1: long arithmetic in a signed type)
+    long long need_level(Coeffs p) const
+    {
+        trim(p);
+        const long long l0 = (long long)x1.level;
+        if (p.size() - 1 < bs) {
+            long long v = l0;
+            for (std::size_t j = 1; j < p.size(); ++j)
+                if (p[j] != 0.0) v = std::min(v, l0 - (long long)clog2(j));
+            return v - 1;
+        }
+        const std::size_t g = split_at(p);
+        const Coeffs quo(p.begin() + (std::ptrdiff_t)g, p.end()), rem(p.begin(), p.begin() + (std::ptrdiff_t)g);
+        long long v = l0 - (long long)clog2(g) - 1;
+        if (above0(quo)) v = std::min(v, need_level(quo) - 1);
+        if (above0(rem)) v = std::min(v, need_level(rem));
+        return v;
+    }
+    // the uses of every power, by the steps and by the powers above it: a power leaves its slot after the last
+    void count_use(std::size_t j)
+    {
+        if (j == 1) return;
+        if (!uses.count(j)) {
+            uses[j] = 0;
+            count_use((j + 1) / 2);
+            count_use(j / 2);
+        }
+        ++uses[j];
+    }
+    void count_eval(Coeffs p)
+    {
+        trim(p);
+        if (p.size() - 1 < bs) {
+            for (std::size_t j = 1; j < p.size(); ++j)
+                if (p[j] != 0.0) count_use(j);
+            return;
+        }
+        const std::size_t g = split_at(p);
+        const Coeffs quo(p.begin() + (std::ptrdiff_t)g, p.end()), rem(p.begin(), p.begin() + (std::ptrdiff_t)g);
+        count_use(g);
+        if (above0(quo)) count_eval(quo);
+        if (above0(rem)) count_eval(rem);
+    }
+    MathVal power(std::size_t j)
+    {
+        if (j == 1) return x1;
+        auto it = pw.find(j);
+        if (it != pw.end()) return it->second;
+        const std::size_t a = (j + 1) / 2, b = j / 2;
+        const MathVal A = power(a), Bv = power(b);
+        const std::size_t lv = std::min(A.level, Bv.level);
+        const MathVal r = prod(down(A, lv), down(Bv, lv));
+        ++nprod;
+        release(a);
+        release(b);
+        pw[j] = r;
+        return r;
+    }
+    void release(std::size_t j)
+    {
+        if (j == 1) return;
+        if (--uses[j] == 0) {
+            drop(pw[j]);
+            pw.erase(j);
+        }
+    }
+
+    // Eval(p, Lt, St): a value at level Lt whose scale is St exactly
+    MathVal eval(Coeffs p, std::size_t Lt, double St)
+    {
+        trim(p);
+        const std::size_t e = p.size() - 1;
+        if (e < bs) {  // leaf: one linear-combination stage
+            const std::size_t l = Lt + 1, off = tab.size();
+            const double T = St * (double)ch.q[Lt];
+            std::vector<MathVal> v;
+            std::vector<std::size_t> js;
+            for (std::size_t j = 1; j <= e; ++j) {
+                if (p[j] == 0.0) continue;
+                const MathVal t = down(power(j), l);
+                const double ps = T / t.scale;
+                tab.resize(tab.size() + l);
+                scalar_words_chain(ch, p[j], ps, l, tab.data() + tab.size() - l);
+                need(ch.scale_ok(t.scale * ps, l), "scale out of bounds");
+                if (!v.empty()) need(are_close(T, T), "scale mismatch");  // add's check: both scales were assigned T
+                v.push_back(t);
+                js.push_back(j);
+            }
+            const std::size_t doff = tab.size();
+            for (const MathVal &t : v) {
+                const std::size_t al = t.alloc ? t.alloc : t.level;
+                tab.push_back((u64)t.slot * slot_words);
+                tab.push_back(2 * al * ring);
+                tab.push_back(al * ring);
+            }
+            u64 dw[HEC_MAXL + 1];
+            MathVal o;
+            o.level = Lt;
+            o.scale = St;
+            if (p[0] != 0.0) {
+                scalar_words_chain(ch, p[0], St, Lt, dw);
+                need(are_close(St, St), "scale mismatch");
+            }
+            o.slot = take();
+            ++nleaf;
+            if (c) {
+                const int nt = (int)v.size();
+                {  // nt sources' last limbs in, the sums out
+                    ProfScope k(*c, "k:k_math_lincomb_last/math", 2.0 * (nt + 1) * B);
+                    math_lincomb_last(*c, slot[0], tab_dev + off, tab_dev + doff, nt, Y, B, 2, (int)l);
+                }
+                stage_round_limbs(*c, Y, Z, B, (int)l, "k:k_ntt/math_intt", "k:k_ntt/math_round_a");
+                {  // Z, every source's data limbs and the outputs, once each
+                    ProfScope k(*c, "k:k_ntt/math_lincomb", 2.0 * (nt + 2) * B * (l - 1));
+                    math_lincomb(*c, Z, slot[0], tab_dev + off, tab_dev + doff, nt, arr(o), B, 2, (int)l,
+                                 p[0] != 0.0 ? dw : nullptr);
+                }
+            }
+            for (std::size_t j : js) release(j);
+            return o;
+        }
+        const std::size_t g = split_at(p);
+        const Coeffs quo(p.begin() + (std::ptrdiff_t)g, p.end()), rem(p.begin(), p.begin() + (std::ptrdiff_t)g);
+        const MathVal X = down(power(g), Lt + 1);
+        const double qs = St * (double)ch.q[Lt] / X.scale;
+        const bool rem_poly = above0(rem);
+        MathVal r;
+        if (above0(quo)) {
+            MathVal Q = eval(quo, Lt + 1, qs);
+            r = prod(Q, X);
+            ++nprod;
+            drop(Q);
+            r.scale = St;
+            if (!rem_poly && rem[0] != 0.0) add_const(r, rem[0]);
+        } else {  // a constant quotient: the scalar stage, the remainder's constant folded into it
+            const bool dc = !rem_poly && rem[0] != 0.0;
+            r = cstage(X, quo[0], dc ? 1 : 0, dc ? rem[0] : 0.0, qs, St);
+        }
+        release(g);
+        if (rem_poly) {
+            MathVal R = eval(rem, Lt, St);
+            add(r, R);
+            drop(R);
+        }
+        return r;
+    }
+
+    // the whole schedule; x at slot 0.  coeffs trimmed and not constant, bs a power of two in [2, 16]
+    MathVal poly(const Coeffs &coeffs, std::size_t bsize, std::size_t level, double scale)
+    {
+        busy.assign(1, 1);
+        peak = 1;
+        bs = bsize;
+        nprod = nleaf = 0;
+        pw.clear();
+        uses.clear();
+        tab.clear();
+        x1 = MathVal{};
+        x1.slot = 0;
+        x1.level = level;
+        x1.scale = scale;
+        if (need_level(coeffs) < 1) throw std::invalid_argument("end of modulus switching chain reached");
+        count_eval(coeffs);
+        return eval(coeffs, (std::size_t)need_level(coeffs), scale);
     }
 
     // he_math.cpp:22-90
@@ -602,7 +837,103 @@ void math_batch(hec_context *ctx, int fn, const hec_ciphertext *const *x, uint64
             store_ct(c, out[b0 + b], dev.slot[(std::size_t)r.slot] + b * So, 2, r.level, r.scale);
     }
 }
+
+// hec_math_poly's argument checks, shared with hec_math_poly_plan: the trimmed coefficients and the block size
+std::size_t poly_args(const double *coeffs, uint64_t degree, uint64_t bs, std::vector<double> &p)
+{
+    need(coeffs, "null argument");
+    need(degree < 65536, "degree must be below 2^16");
+    p.assign(coeffs, coeffs + degree + 1);
+    for (double v : p) need(std::isfinite(v), "coefficients must be finite");
+    MathRun::trim(p);
+    need(p.size() >= 2, "polynomial must not be constant");
+    if (bs == 0) {
+        const std::size_t m = std::min<std::size_t>(4, std::max<std::size_t>(1, (MathRun::clog2(p.size()) + 1) / 2));
+        bs = uint64_t(1) << m;
+    }
+    need(bs >= 2 && bs <= 16 && !(bs & (bs - 1)), "bs must be a power of two in [2, 16]");
+    return (std::size_t)bs;
+}
+
+void poly_batch(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, const double *coeffs, uint64_t degree,
+                uint64_t bs, const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    need(ctx && x && out && B >= 1, "null argument");
+    set_device(ctx);
+    check_uniform_batch(ctx, x, out, B);
+    check_obj(ctx, rk, BAD_RK);
+    std::vector<double> p;
+    const std::size_t bse = poly_args(coeffs, degree, bs, p);
+    Ctx &c = ctx->c;
+    const std::size_t N = c.N, l0 = x[0]->level, S0 = 2 * l0 * N;
+    const std::size_t Bc = batch_chunk(c, l0, B);
+    MathRun plan;
+    plan.ch = Chain{c.q.data(), c.L};
+    plan.ring = N;
+    plan.slot_words = Bc * S0;  // a multiple of 64: the carves below are back to back
+    const MathVal res = plan.poly(p, bse, l0, x[0]->scale);
+    const std::size_t nslot = (std::size_t)plan.peak, ntab = std::max<std::size_t>(plan.tab.size(), 1);
+    Scratch s(c, nslot * Bc * S0 + Bc * 3 * l0 * N + 2 * Bc * N + 2 * Bc * l0 * N + ks_words(c, Bc, l0) +
+                     rescale_words(c, Bc, 2, l0) + ntab + (nslot + 17) * 64);
+    MathRun dev;
+    dev.ch = plan.ch;
+    dev.c = &c;
+    dev.s = &s;
+    dev.rk = rk->d;
+    dev.ring = N;
+    dev.slot_words = plan.slot_words;
+    for (std::size_t i = 0; i < nslot; ++i) {
+        dev.slot.push_back(s.take(Bc * S0));
+        if (dev.slot[i] != dev.slot[0] + i * plan.slot_words) throw std::logic_error("he::math slots are not contiguous");
+    }
+    dev.T3 = s.take(Bc * 3 * l0 * N);
+    dev.Y = s.take(2 * Bc * N);
+    dev.Z = s.take(2 * Bc * l0 * N);
+    // every leaf's coefficient words, once per call, ahead of the first pass on the context's stream
+    u64 *tabd = s.take(ntab);
+    if (!plan.tab.empty()) {
+        HEC_HIP(hipMemcpyAsync(tabd, plan.tab.data(), plan.tab.size() * sizeof(u64), hipMemcpyHostToDevice, c.stream));
+        HEC_HIP(hipStreamSynchronize(c.stream));  // the copy has left the host table before anything can throw
+    }
+    dev.tab_dev = tabd;
+    const std::size_t So = 2 * res.level * N;
+    for (std::size_t b0 = 0; b0 < B; b0 += Bc) {
+        const std::size_t cnt = std::min(Bc, B - b0);
+        dev.B = (int)cnt;
+        for (std::size_t b = 0; b < cnt; ++b) d2d(c, dev.slot[0] + b * S0, x[b0 + b]->d, S0);
+        const MathVal r = dev.poly(p, bse, l0, x[0]->scale);
+        for (std::size_t b = 0; b < cnt; ++b)
+            store_ct(c, out[b0 + b], dev.slot[(std::size_t)r.slot] + b * So, 2, r.level, r.scale);
+    }
+}
 }  // namespace
+
+int hec_math_poly_plan(const uint64_t *coeff_modulus, uint64_t K, const double *coeffs, uint64_t degree, uint64_t bs,
+                       uint64_t level, double scale, uint64_t *out_level, double *out_scale, uint64_t *bs_eff,
+                       uint64_t *products, uint64_t *leaves)
+{
+    return guard([&] {
+        need(coeff_modulus && out_level && out_scale && bs_eff && products && leaves, "null argument");
+        need(K >= 2 && K - 1 <= HEC_MAXL, "coeff_modulus size is not valid");
+        need(level >= 1 && level <= K - 1, BAD_CT);
+        std::vector<double> p;
+        const std::size_t bse = poly_args(coeffs, degree, bs, p);
+        MathRun plan;
+        plan.ch = Chain{coeff_modulus, (std::size_t)(K - 1)};
+        const MathVal r = plan.poly(p, bse, level, scale);
+        *out_level = r.level;
+        *out_scale = r.scale;
+        *bs_eff = bse;
+        *products = plan.nprod;
+        *leaves = plan.nleaf;
+    });
+}
+
+int hec_math_poly(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, const double *coeffs, uint64_t degree,
+                  uint64_t bs, const hec_kswitch_key *rk, hec_ciphertext *const *out)
+{
+    return guard([&] { poly_batch(ctx, x, B, coeffs, degree, bs, rk, out); });
+}
 
 int hec_math_plan(const uint64_t *coeff_modulus, uint64_t K, int fn, double a, uint64_t iter_num, uint64_t level,
                   double scale, uint64_t *out_level, double *out_scale)

@@ -14,6 +14,7 @@ typedef uint64_t u64;
 typedef uint32_t u32;
 
 #define HEC_MAXL 32  // max RNS limbs handled by per-limb constant tables passed by value
+#define HEC_MATH_MAXT 15  // max terms of he::math's linear-combination stage (a leaf of block size 16)
 
 struct DevPrime {
     u64 q;

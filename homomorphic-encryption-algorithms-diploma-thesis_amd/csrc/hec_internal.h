@@ -409,5 +409,15 @@ void math_lastprod(Ctx &c, const u64 *A, u64 a_sb, u64 a_sk, u64 *Y, int B, int 
 void math_cstage(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, PolyArr OUT, int B, int nk, int l,
                  const u64 *cw, const u64 *dw);
 void math_tensor(Ctx &c, PolyArr A, PolyArr Bp, const u64 *dw, u64 *OUT, int B, int l);
+// Linear-combination stage OUT = rescale(sum_t A_t (*) c_t) + d, 1 to HEC_MATH_MAXT sources of their own bases and
+// strides, all read at level l: math_lincomb_last forms the last-limb sums Y (then the batched INTT and
+// fft_round_limbs give Z), math_lincomb is the fused pass B.  On the device: C, the coefficient words, word [t l + i];
+// D, three words per source: its offset from A0, its entry stride and its poly stride, in words (every one a
+// multiple of 2, so that word pairs stay aligned).
+// math_addconst: X[b].c0 += d in place over B entries of nl limbs (add_plain of a scalar)
+void math_lincomb_last(Ctx &c, const u64 *A0, const u64 *C, const u64 *D, int nt, u64 *Y, int B, int nk, int l);
+void math_lincomb(Ctx &c, const u64 *Z, const u64 *A0, const u64 *C, const u64 *D, int nt, PolyArr OUT, int B, int nk,
+                  int l, const u64 *dw);
+void math_addconst(Ctx &c, PolyArr X, const u64 *dw, int B, int nl);
 
 }  // namespace hec

@@ -225,6 +225,12 @@ template <class T, class = void>
 struct HasLatePre : std::false_type {};
 template <class T>
 struct HasLatePre<T, std::void_t<decltype(T::kLatePre)>> : std::bool_constant<T::kLatePre> {};
+// Bound types that form all of a thread's late operands in one call, pre_block<ITS>(pre, g of it) (HasPreBlock): a
+// sum over many sources walks the sources in its outer loop
+template <class T, class = void>
+struct HasPreBlock : std::false_type {};
+template <class T>
+struct HasPreBlock<T, std::void_t<decltype(T::kPreBlock)>> : std::bool_constant<T::kPreBlock> {};
 // Bound types whose final store may write the MAC form (a run-time flag `mform`, HasMForm)
 template <class T, class = void>
 struct HasMForm : std::false_type {};
@@ -776,7 +782,13 @@ __device__ __forceinline__ void ntt_pass_body(u64 *lds, const Bound &bio, const 
         }
         return;
     }
-    if constexpr (FINAL && LATE && !PAIR) {  // the operands now, all issued before the first store
+    if constexpr (FINAL && LATE && !PAIR && HasPreBlock<Bound>::value) {  // the operands now, operand by operand
+        bio.template pre_block<ITS>(pre, [&](int it) -> u64 {
+            const int li = threadIdx.x + it * THREADS;
+            if constexpr (PASS_A) return ((u64)(li / NSEG) << lc) + seg0 + li % NSEG;
+            else return ((u64)(seg0 + li / P) << LOGP) + li % P;
+        });
+    } else if constexpr (FINAL && LATE && !PAIR) {  // the operands now, all issued before the first store
 #pragma unroll
         for (int it = 0; it < ITS; ++it) {
             const int li = threadIdx.x + it * THREADS;
@@ -1420,14 +1432,216 @@ void math_cstage(Ctx &c, const u64 *Z, const u64 *A, u64 a_sb, u64 a_sk, PolyArr
     ntt_dispatch<false>(c, B * nk * nl, DivRoundIO_A{}, b, 2);
 }
 
+// The linear-combination stage of he::math (math_lincomb_last, math_lincomb): OUT = rescale(sum_t A_t (*) c_t) + d over
+// B entries, 1 to HEC_MATH_MAXT terms: the inner sum of a polynomial's leaf.  It generalises the scalar stage: the
+// rounding limb z comes from the sum's own last limb, so one INTT, one rounding pass and one pass B serve all terms,
+// and neither a product nor a partial sum is stored.  Every source has its own base and strides (a power is read at
+// a lower level than its slot was written at).  15 terms of l words do not fit the kernel arguments, so the stage
+// reads a device table that the call uploads once: C, the coefficient words c_t,i at [t cs + i], and D, three words
+// per source: its offset from A0 and its entry and poly strides, in words.  The terms are walked in the outer loop and
+// a thread's outputs in the inner one (pre_block), so a term's descriptor and coefficient are wave-uniform scalars,
+// one load per output is in flight at a time and the registers do not grow with the number of terms.
+//   FP64 primes (q < 2^42): every term is one exact fp_mulmod, an integer in [-0.53 q, 0.53 q], so the sum of 15 is an
+//   integer of magnitude <= 7.95 q < 2^45: exact in a double and inside what fp_canon takes (|x| < 2^52).  The sum
+//   is canonicalised before pass B's post-op, so |x - v| < q + 10 q = 11 q there, MathIOB's bound.
+//   Integer primes: one 128-bit sum of the products (15 products of words below 2^60 stay below 2^124) and one
+//   barrett128.
+// Both give the canonical residue of the exact sum, so the bits equal multiply_plain, add x (T - 1), rescale_to_next,
+// add_plain in turn.
+struct MathConst {  // a scalar plaintext's words, one per limb
+    u64 d[HEC_MAXL];
+};
+
+struct MathLinIOB {
+    const u64 *Z, *A0, *C, *D;
+    PolyArr OUT;
+    int nt, cs, nk, nl, logN;
+    const DevPrime *primes;
+    u64 d[HEC_MAXL], inv[HEC_MAXL], inv_q[HEC_MAXL];
+    struct Bound {
+        static constexpr bool kFpStore = true;
+        static constexpr bool kLatePre = true;   // the operands are loaded at the store
+        static constexpr bool kPreBlock = true;  // all of a thread's operands at once, term by term
+        const u64 *z, *a0, *cw, *D;  // a0: A0 at limb i; cw: C at limb i
+        u64 *out;
+        DevPrime pr;
+        u64 d, w, wq, b, k;
+        int nt, cs, prime;
+        bool fpstore = true;
+        bool valid = true;
+        struct Pre {
+            u64 x;  // sum_t a_t c_t mod q, canonical
+        };
+        __device__ const u64 *src(int t) const { return a0 + D[3 * t] + b * D[3 * t + 1] + k * D[3 * t + 2]; }
+        template <int ITS, class G>
+        __device__ void pre_block(Pre (&pre)[ITS], G gof) const
+        {
+            if (pr.fp) {
+                double s[ITS];
+#pragma unroll
+                for (int it = 0; it < ITS; ++it) s[it] = 0;
+#pragma unroll 1
+                for (int t = 0; t < nt; ++t) {
+                    const u64 *at = src(t);
+                    const double cd = u2d(cw[t * cs]);
+#pragma unroll
+                    for (int it = 0; it < ITS; ++it) s[it] += fp_mulmod(u2d(at[gof(it)]), cd, pr.qd, pr.qinv);
+                }
+#pragma unroll
+                for (int it = 0; it < ITS; ++it) pre[it].x = fp_canon(s[it], pr.qd, pr.qinv);  // |s| <= 7.95 q
+                return;
+            }
+            U128 s[ITS];
+#pragma unroll
+            for (int it = 0; it < ITS; ++it) s[it] = U128{0, 0};
+#pragma unroll 1
+            for (int t = 0; t < nt; ++t) {
+                const u64 *at = src(t);
+                const u64 cv = cw[t * cs];
+#pragma unroll
+                for (int it = 0; it < ITS; ++it) mac128(s[it], at[gof(it)], cv);
+            }
+#pragma unroll
+            for (int it = 0; it < ITS; ++it) pre[it].x = barrett128(s[it].lo, s[it].hi, pr.q, pr.r0, pr.r1);
+        }
+        __device__ Pre pre(u64 g) const  // one word (the passes without pre_block)
+        {
+            Pre p[1];
+            pre_block<1>(p, [g](int) { return g; });
+            return p[0];
+        }
+        __device__ u64 load(u64 g) const { return z[g]; }
+        __device__ void store(u64 g, u64 v, Pre p) const
+        {
+            out[g] = addmod(shoup(p.x + pr.q - v, w, wq, pr.q), d, pr.q);
+        }
+        // |x - v| < 11 q as in MathIOB: x is canonical, |v| < 10 q
+        __device__ void store_fp(u64 g, double v, Pre p, const DevPrime &) const
+        {
+            const double r = fp_mulmod(u2d(p.x) - v, u2d(w), pr.qd, pr.qinv) + u2d(d);
+            out[g] = fp_canon(r, pr.qd, pr.qinv);
+        }
+    };
+    __device__ Bound bind(int job) const
+    {
+        const int i = job % nl, t = job / nl, k = t % nk, b = t / nk;
+        const u64 li = (u64)i << logN;
+        Bound bo;
+        bo.z = Z + ((u64)job << logN);
+        bo.a0 = A0 + li;
+        bo.cw = C + i;
+        bo.D = D;
+        bo.out = OUT.p + b * OUT.sb + k * OUT.sk + li;
+        bo.pr = primes[i];
+        bo.d = k == 0 ? d[i] : 0;
+        bo.w = inv[i];
+        bo.wq = inv_q[i];
+        bo.b = (u64)b;
+        bo.k = (u64)k;
+        bo.nt = nt;
+        bo.cs = cs;
+        bo.prime = i;
+        return bo;
+    }
+};
+
+// Y[(b nk + k)][g] = sum_t A_t[b][k][last][g] c_t,last mod q_last: the last-limb sums of the linear-combination stage,
+// two words (16 bytes) per lane; every source word is read once
+__global__ void __launch_bounds__(256)
+    k_math_lincomb_last(const u64 *__restrict__ A0, const u64 *__restrict__ C, const u64 *__restrict__ D, int nt, int cs,
+                        u64 *__restrict__ Y, int nk, int logN, int last, u64 pairs, const DevPrime *__restrict__ primes)
+{
+    const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pairs) return;
+    const u64 idx = 2 * p, g = idx & ((1ull << logN) - 1), e = idx >> logN;
+    const u64 k = e % (u64)nk, b = e / (u64)nk;
+    const u64 *a0 = A0 + ((u64)last << logN);
+    const DevPrime pr = primes[last];
+    u64 x, y;
+    if (pr.fp) {
+        double sx = 0, sy = 0;
+        for (int t = 0; t < nt; ++t) {
+            const ulonglong2 a = ld2(a0 + D[3 * t] + b * D[3 * t + 1] + k * D[3 * t + 2], g);
+            const double cd = u2d(C[t * cs + last]);
+            sx += fp_mulmod(u2d(a.x), cd, pr.qd, pr.qinv);
+            sy += fp_mulmod(u2d(a.y), cd, pr.qd, pr.qinv);
+        }
+        x = fp_canon(sx, pr.qd, pr.qinv);  // |sx| <= 7.95 q
+        y = fp_canon(sy, pr.qd, pr.qinv);
+    } else {
+        U128 sx{0, 0}, sy{0, 0};
+        for (int t = 0; t < nt; ++t) {
+            const ulonglong2 a = ld2(a0 + D[3 * t] + b * D[3 * t + 1] + k * D[3 * t + 2], g);
+            const u64 cv = C[t * cs + last];
+            mac128(sx, a.x, cv);
+            mac128(sy, a.y, cv);
+        }
+        x = barrett128(sx.lo, sx.hi, pr.q, pr.r0, pr.r1);
+        y = barrett128(sy.lo, sy.hi, pr.q, pr.r0, pr.r1);
+    }
+    st2(Y, idx, x, y);
+}
+
+void math_lincomb_last(Ctx &c, const u64 *A0, const u64 *C, const u64 *D, int nt, u64 *Y, int B, int nk, int l)
+{
+    if (nt < 1 || nt > HEC_MATH_MAXT) throw std::invalid_argument("math_lincomb: 1 to HEC_MATH_MAXT terms");
+    const u64 pairs = (u64)B * nk * c.N / 2;
+    k_math_lincomb_last<<<(unsigned)((pairs + 255) / 256), 256, 0, c.stream>>>(A0, C, D, nt, l, Y, nk, c.logN, l - 1,
+                                                                              pairs, c.primes);
+    HEC_HIP(hipGetLastError());
+}
+
+// the linear-combination stage's pass B (MathLinIOB) over B entries of nk polys at level l -> OUT at level l - 1; Z
+// from fft_round_limbs; C: nt x l coefficient words and D: nt x 3 source words on the device; dw == nullptr: no
+// constant is added
+void math_lincomb(Ctx &c, const u64 *Z, const u64 *A0, const u64 *C, const u64 *D, int nt, PolyArr OUT, int B, int nk,
+                  int l, const u64 *dw)
+{
+    const int nl = l - 1;
+    if (nl < 1 || nl > HEC_MAXL) throw std::invalid_argument("math_lincomb: 1 to HEC_MAXL output limbs");
+    if (nt < 1 || nt > HEC_MATH_MAXT) throw std::invalid_argument("math_lincomb: 1 to HEC_MATH_MAXT terms");
+    MathLinIOB b{};
+    b.Z = Z; b.A0 = A0; b.C = C; b.D = D; b.OUT = OUT; b.nt = nt; b.cs = l; b.nk = nk; b.nl = nl;
+    b.logN = c.logN; b.primes = c.primes;
+    for (int i = 0; i < nl; ++i) {
+        b.d[i] = dw ? dw[i] : 0;
+        b.inv[i] = c.ql_inv[l][i];
+        b.inv_q[i] = c.ql_inv_q[l][i];
+    }
+    ntt_dispatch<false>(c, B * nk * nl, DivRoundIO_A{}, b, 2);
+}
+
+// OUT[b].c0 += d: add_plain of a scalar plaintext (one word per limb) to B entries at nl limbs, two words per lane
+__global__ void __launch_bounds__(256)
+    k_math_addconst(PolyArr X, MathConst dc, int nl, int logN, u64 pairs, const DevPrime *__restrict__ primes)
+{
+    const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pairs) return;
+    const u64 idx = 2 * p;
+    const int i = (int)(idx >> logN);
+    const u64 q = primes[i].q, d = dc.d[i];
+    u64 *x = X.p + (u64)blockIdx.y * X.sb;
+    const ulonglong2 v = ld2(x, idx);
+    st2(x, idx, addmod(v.x, d, q), addmod(v.y, d, q));
+}
+
+void math_addconst(Ctx &c, PolyArr X, const u64 *dw, int B, int nl)
+{
+    if (nl < 1 || nl > HEC_MAXL) throw std::invalid_argument("math_addconst: 1 to HEC_MAXL limbs");
+    if (B < 1 || B > 65535) throw std::invalid_argument("math_addconst: 1 to 65535 jobs");
+    MathConst dc{};
+    for (int i = 0; i < nl; ++i) dc.d[i] = dw[i];
+    const u64 pairs = (u64)nl * c.N / 2;
+    k_math_addconst<<<dim3((unsigned)((pairs + 255) / 256), (unsigned)B), 256, 0, c.stream>>>(X, dc, nl, c.logN, pairs,
+                                                                                             c.primes);
+    HEC_HIP(hipGetLastError());
+}
+
 // The product stage's tensor (k_math_tensor): OUT[b] = A[b] (x) (B'[b] + d), sizes 2 x 2 -> 3, B jobs along grid y,
 // in the [B][3][l][N] layout keyswitch() takes.  same: B' is A (the square), each word read once.  d (has_d): a
 // scalar plaintext's words added to B'.c0 on load, so the operand "e^2 + 1" of signed_inv is never stored.  Products as
 // SEAL reduces them, FP64 for the primes below 2^42 (exact fp_mulmod, |sum| <= 1.06 q) and 128-bit sums otherwise;
 // canonical outputs, so the bits are those of multiply / square after add_plain.  Two words (16 bytes) per lane.
-struct MathConst {
-    u64 d[HEC_MAXL];
-};
 __global__ void __launch_bounds__(256)
     k_math_tensor(PolyArr A, PolyArr Bp, int same, int has_d, MathConst dc, u64 *__restrict__ OUT, int l, int logN,
                   u64 pairs, const DevPrime *__restrict__ primes)

@@ -463,6 +463,27 @@ int hec_math_sqrt(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, 
 /* abs (he_math.cpp:237-269): inv_sqrt_twice(x^2, 1 / a / sqrt 2) times sqrt(2) x^2 dropped to its level */
 int hec_math_abs(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, double a, uint64_t iter_num,
                  const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* Polynomial evaluation, an extension (the reference has none): out[i] = sum_j coeffs[j] x[i]^j, j = 0 .. degree, by
+ * Paterson-Stockmeyer with block size bs (a power of two in [2, 16]; 0 chooses 2^m, m = min(4, max(1, ceil(ceil(log2(
+ * d + 1)) / 2)))), on B ciphertexts at once.  out[i] is, bit for bit with its level and scale, what the per-operation
+ * schedule of DESIGN.md 2.9 gives for x[i] alone: x^j = rescale(relin(x^ceil(j/2) x^floor(j/2))) after
+ * mod_switch_to_next to the lower level, each power once; a leaf (degree below bs) is the sum of multiply_plain by
+ * scalar encodes whose scales land every term on one assigned scale, rescaled once, plus add_plain of the constant; a
+ * node is Eval(quotient) x^g + Eval(remainder), g = bs 2^k <= degree.  The output scale is the input scale bitwise and
+ * the output level is the one hec_math_poly_plan reports (a dense polynomial of degree 7 or 8 takes four levels, of
+ * degree 63 seven).  Real finite coefficients
+ * ("coefficients must be finite"); trailing zeros are trimmed and what remains must not be constant ("polynomial
+ * must not be constant"); degree < 2^16 ("degree must be below 2^16"); "bs must be a power of two in [2, 16]".  A
+ * coefficient that is exactly 0.0 issues no step.  Inputs, rk, passes, the order of the host checks and their messages
+ * as the calls above; nothing is written on an error.  out[i] may be a fresh handle or x[i]. */
+int hec_math_poly(hec_context *ctx, const hec_ciphertext *const *x, uint64_t B, const double *coeffs, uint64_t degree,
+                  uint64_t bs, const hec_kswitch_key *rk, hec_ciphertext *const *out);
+/* host only, no device: the level and scale hec_math_poly would return for inputs at (level, scale), the block size
+ * it uses, its products (relinearised multiplications, the powers included) and its leaves (linear-combination
+ * stages); or the status and message of the first check that fails.  coeff_modulus: the K key moduli */
+int hec_math_poly_plan(const uint64_t *coeff_modulus, uint64_t K, const double *coeffs, uint64_t degree, uint64_t bs,
+                       uint64_t level, double scale, uint64_t *out_level, double *out_scale, uint64_t *bs_eff,
+                       uint64_t *products, uint64_t *leaves);
 /* he::util::drop_chain_levels (he_util.h:27-48) on B ciphertexts in place: per level, every ciphertext times the
  * scalar encode of 1 at the first one's level and scale, rescaled.  Inputs and errors as above; levels = 0 is a no-op */
 int hec_drop_chain_levels(hec_context *ctx, hec_ciphertext *const *cts, uint64_t B, uint64_t levels);
