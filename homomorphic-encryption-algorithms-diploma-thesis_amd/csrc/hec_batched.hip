@@ -3,7 +3,7 @@
 // hec_sum_elems_many), C-ABI of include/hecdna.h.
 //
 // Each layer is host orchestration over the engine's building blocks (hec_host.h: the key switch with its Galois and
-// relinearize-and-rescale forms, the output store, the checks; defined in hec_engine.hip) and the stage kernels behind
+// relinearize-and-rescale forms, the output store, the checks; defined in the engine's files) and the stage kernels behind
 // hec_internal.h.  A call checks everything first, gathers its inputs into slots of one Scratch workspace, runs its
 // stages over the whole batch in passes, and stores the outputs after the last stage.  The plumbing the three layers
 // share comes first.

@@ -1,7 +1,8 @@
-// Host-side internals shared by hec_engine.hip (the objects' lifecycle, the key switch, the matvec, the evaluator) and
-// hec_batched.hip (he::fft, he::math and he::linalg over many ciphertexts): the device objects behind the C-ABI's
-// opaque types, the error guard, the workspace carver, the profile scope, and declarations of the engine's building
-// blocks that the batched layers are written over (defined in hec_engine.hip).
+// Host-side internals shared by the engine's files (hec_engine.hip: the objects' lifecycle, the matvec, the evaluator;
+// hec_keyswitch.hip: the key switch; what crosses between those two alone is in hec_engine.h) and hec_batched.hip
+// (he::fft, he::math and he::linalg over many ciphertexts): the device objects behind the C-ABI's opaque types, the
+// error guard, the workspace carver, the profile scope, and declarations of the engine's building blocks that the
+// batched layers are written over (defined in hec_engine.hip and hec_keyswitch.hip).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -232,9 +233,10 @@ struct Chain {
     }
 };
 
-// ------------------------------------------------------------------ building blocks (hec_engine.hip)
-// Only what hec_batched.hip calls.  keyswitch(), rescale_batch(), grow() and make() stay private to the engine: the
-// batched layers reach them through galois_ks(), relin_rescale() and store_ct().
+// ------------------------------------------------------------------ building blocks (hec_engine.hip, hec_keyswitch.hip)
+// Only what hec_batched.hip calls.  keyswitch(), rescale_batch(), grow() and make() stay private to the engine (the
+// first two cross its files through hec_engine.h): the batched layers reach them through galois_ks(), relin_rescale()
+// and store_ct().
 void set_device(hec_context *ctx);
 // Calls that take a context: the object must belong to this very context
 void check_obj(const hec_context *ctx, const DevObject *o, const char *msg);

@@ -146,7 +146,7 @@ struct Ctx {
     bool kernel_memops = true;
     int prng_group = 0;            // option "prng_group": PRNG buffers per wavefront of k_prng (hec_keygen.hip), 1 .. 16;
                                    // 0 picks the largest that still fills the device.  Every value draws the same words
-    int rot_add = 1;               // option "rot_add": 1 a key switch's optional addend ADD (keyswitch() in hec_engine.hip) is
+    int rot_add = 1;               // option "rot_add": 1 a key switch's optional addend ADD (keyswitch() in hec_keyswitch.hip) is
                                    // added in its last stage (k_bmac's divide-and-round epilogue, k_moddown1); 0 by a
                                    // k_ew_add launch after it.  Same words
     int math_chunk = 0;            // option "math_chunk": ciphertexts per pass of the he::math calls, 0 automatic (the
@@ -190,7 +190,7 @@ struct Ctx {
 // stages: 1 first pass only, 2 second pass only, 3 both.
 void ntt_strided(Ctx &c, bool inverse, const u64 *src, u64 ps_src, u64 *dst, u64 ps_dst, int nl, const int *pmap,
                  int njobs, u32 elt = 1, int stages = 3);
-// Key-switch phases (B targets at level l; see hec_engine.hip for the dataflow)
+// Key-switch phases (B targets at level l; see hec_keyswitch.hip for the dataflow)
 void ks_modup(Ctx &c, const u64 *D, u64 *E, int B, int l, int stages = 3,
               bool mform = false);  // stages as ntt_strided; mform: E in the MAC form k_hmacm reads
 void ks_mac(Ctx &c, PolyArr T, const u64 *E, const u64 *key, u64 *ACC, int B, int l, u32 elt);

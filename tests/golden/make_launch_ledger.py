@@ -29,6 +29,7 @@ class Env:
         self.rk = self.ctx.relin_key(seed=11)
         self.gk = self.ctx.galois_keys(uniform_elts=[self.ctx.elt_from_step(s) for s in STEPS], seed=5)
         self.seed = 100
+        self.client = None
 
     def cts(self, count, level=LEVEL, size=2, scale=SCALE):
         out = []
@@ -43,6 +44,19 @@ class Env:
             self.seed += 1
             out.append(self.ctx.plaintext(None, scale).fill_uniform(level, scale, self.seed))
         return out
+
+    def client_keys(self):
+        """(sk, pk) of the client-half calls, generated once from fixed seeds on first use (outside any profile when
+        the call's unprofiled run comes first, as record() runs it)"""
+        if self.client is None:
+            sk = self.ctx.keygen_secret(seed=_seed(1))
+            self.client = (sk, self.ctx.keygen_public(sk, seed=_seed(2)))
+        return self.client
+
+
+def _seed(k):
+    """a fixed 64-byte seed: the generating calls are pure functions of it, the uniform sampler's redraws included"""
+    return [k, 2, 3, 4, 5, 6, 7, 8]
 
 
 def _chunked(fn):
@@ -95,6 +109,53 @@ def _square(e):
     e.ctx.multiply_relin_rescale(a, a, e.rk)
 
 
+# 3 columns, p = 5, bs = 2: G = 3, baby step 1, giants -2 and -4 (the natural form rotates by +2 and +4 as well), all of
+# them keys of STEPS
+def _cct(bsgs_form):
+    def run(e):
+        e.ctx.matmul_col_colT_bsgs(e.cts(3), e.cts(3), 5, e.rk, e.gk, bs=2, bsgs_form=bsgs_form)
+    return run
+
+
+def _jchunk2(fn):
+    """the call in passes of 2 columns and 1 column: the assigning launch and the accumulating launch"""
+    def run(e):
+        e.ctx.set_option("cct_jchunk", 2)
+        try:
+            fn(e)
+        finally:
+            e.ctx.set_option("cct_jchunk", 0)
+    return run
+
+
+def _multiply(e):
+    a, b = e.cts(2)
+    e.ctx.multiply(a, b)
+
+
+# The client half.  hec_encode and hec_encode_scalar record no profile class, so they have no entry here (the bit-exact
+# suites carry them); every generating call takes a fixed seed
+def _keygen_galois(e):
+    sk, _ = e.client_keys()
+    e.ctx.keygen_galois(sk, elts=[e.ctx.elt_from_step(1), e.ctx.elt_from_step(2)], seed=_seed(4))
+
+
+def _decrypt(e):
+    e.ctx.decrypt(e.client_keys()[0], e.cts(2))
+
+
+def _decrypt_decode(e):
+    e.ctx.decrypt_decode(e.client_keys()[0], e.cts(2), n_values=8)
+
+
+def _encrypt_symmetric(e):
+    e.ctx.encrypt_symmetric(e.client_keys()[0], e.pts(2), seed=_seed(5))
+
+
+def _encrypt(e):
+    e.ctx.encrypt(e.client_keys()[1], e.pts(2), seed=_seed(6))
+
+
 # name -> call; the inputs are made inside the call (fills carry no profile scope)
 CALLS = {
     "sum_elems_B3_dim7": lambda e: e.ctx.sum_elems(e.cts(3), 7, e.gk),
@@ -119,6 +180,26 @@ CALLS = {
     "bsgs_ct_n10_p3_bs4": _bsgs_ct,
     "bsgs_pt_n10_p3_bs4_gg2_chunk2": _bsgs_small("bsgs_gg", _bsgs_pt),
     "bsgs_ct_n10_p3_bs4_gg2_chunk2": _bsgs_small("bsgs_ct_gg", _bsgs_ct),
+    "cct_bsgs_n3_p5_bs2_natural": _cct(False),
+    "cct_bsgs_n3_p5_bs2_bsgs_form": _cct(True),
+    "cct_bsgs_n3_p5_bs2_natural_jchunk2": _jchunk2(_cct(False)),
+    "cct_bsgs_n3_p5_bs2_bsgs_form_jchunk2": _jchunk2(_cct(True)),
+    "rotate_vector_step3_inplace": lambda e: e.ctx.rotate_vector(e.cts(1)[0], 3, e.gk),  # 3 = 4 - 1: a NAF chain
+    "apply_galois_inplace": lambda e: e.ctx.apply_galois(e.cts(1)[0], e.ctx.elt_from_step(1), e.gk),
+    # multiply and square carry no profile scope: their entries are empty and must stay so
+    "multiply_inplace": _multiply,
+    "square_inplace": lambda e: e.ctx.square(e.cts(1)[0]),
+    # no communicator: the world of one, in this process (planner, partials, finish)
+    "matmul_diag_col_sharded_world1_n10_p2": lambda e: e.ctx.matmul_diag_col_sharded(e.cts(10), e.cts(2), e.rk, e.gk),
+    "keygen_secret": lambda e: e.ctx.keygen_secret(seed=_seed(1)),
+    "keygen_public": lambda e: e.ctx.keygen_public(e.client_keys()[0], seed=_seed(2)),
+    "keygen_relin": lambda e: e.ctx.keygen_relin(e.client_keys()[0], seed=_seed(3)),
+    "keygen_galois_2elts": _keygen_galois,
+    "encrypt_symmetric_B2": _encrypt_symmetric,
+    "encrypt_B2": _encrypt,
+    "decrypt_B2": _decrypt,
+    "decode_B2_nv8": lambda e: e.ctx.decode(e.pts(2), n_values=8),
+    "decrypt_decode_B2_nv8": _decrypt_decode,
 }
 
 

@@ -1,6 +1,9 @@
 """The launch ledger: for a fixed list of engine calls (tests/golden/make_launch_ledger.py: the batched he::linalg,
 he::math and he::fft calls, the matvec family with both baby-step giant-step forms (whole, and in tiles of 2 giants and
-passes of 2 vectors) and two evaluator calls, at N = 2^11 over {60, 40, 40, 40, 40, 60}),
+passes of 2 vectors), the baby-step giant-step col x col^T product in both output forms (whole, and in passes of 2
+columns), the sharded matvec on a world of one, the evaluator's relinearize, rescale, rotate_vector, apply_galois,
+multiply and square, and the client half (keygen_*, encrypt*, decrypt, decode; encode records no class and has no
+entry), at N = 2^11 over {60, 40, 40, 40, 40, 60}),
 every profile class a call touches must show the scopes, kernel launches and algorithmic bytes recorded in
 tests/golden/launch_ledger.json, and no other class.  The fixture is recorded at the commit before a change that must
 leave the launch sequence alone, so a moved, lost or doubled launch fails here even where the words stay right.
