@@ -1,8 +1,10 @@
-// Host-side internals shared by the engine's files (hec_engine.hip: the objects' lifecycle, the matvec, the evaluator;
-// hec_keyswitch.hip: the key switch; what crosses between those two alone is in hec_engine.h) and hec_batched.hip
-// (he::fft, he::math and he::linalg over many ciphertexts): the device objects behind the C-ABI's opaque types, the
-// error guard, the workspace carver, the profile scope, and declarations of the engine's building blocks that the
-// batched layers are written over (defined in hec_engine.hip and hec_keyswitch.hip).
+// Host-side internals shared by the engine's files (hec_engine.hip: context, objects, primitives; hec_keyswitch.hip:
+// the key switch; hec_matvec.hip: the he::linalg drivers; hec_shard.hip: the multi-GPU calls; hec_client.hip: encode,
+// decode, keygen, encrypt; hec_evaluator.hip: the one-object calls; what crosses between those alone is in
+// hec_engine.h) and hec_batched.hip (he::fft, he::math and he::linalg over many ciphertexts): the device objects behind
+// the C-ABI's opaque types, the error guard, the workspace carver, the profile scope, and declarations of the engine's
+// building blocks that the batched layers are written over (defined in hec_engine.hip, hec_keyswitch.hip and
+// hec_client.hip).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -233,10 +235,11 @@ struct Chain {
     }
 };
 
-// ------------------------------------------------------------------ building blocks (hec_engine.hip, hec_keyswitch.hip)
-// Only what hec_batched.hip calls.  keyswitch(), rescale_batch(), grow() and make() stay private to the engine (the
-// first two cross its files through hec_engine.h): the batched layers reach them through galois_ks(), relin_rescale()
-// and store_ct().
+// ------------------------------------------------------------------ building blocks (hec_engine.hip, hec_keyswitch.hip,
+// hec_client.hip)
+// Only what hec_batched.hip calls.  keyswitch(), rescale_batch(), grow() and make() stay private to the engine (they
+// cross its files through hec_engine.h): the batched layers reach them through galois_ks(), relin_rescale() and
+// store_ct().
 void set_device(hec_context *ctx);
 // Calls that take a context: the object must belong to this very context
 void check_obj(const hec_context *ctx, const DevObject *o, const char *msg);

@@ -63,7 +63,7 @@ def ks_count(N, n, elts=None):
 
 
 def rotation_trie_stats(N, n, min_children=2):
-    """The engine's rotation prefix trie for j = 1..n-1 (csrc/hec_engine.hip RotTrie): SEAL's key-switch
+    """The engine's rotation prefix trie for j = 1..n-1 (csrc/hec_matvec.hip RotTrie): SEAL's key-switch
     sequence per rotation (one key for +-2^i, else the NAF terms, least significant first).  Returns
     (key switches, hoisted nodes, children of hoisted nodes, children of the other nodes); a node is
     hoisted when it has at least min_children children (HEC_HOIST_MIN)."""

@@ -388,7 +388,7 @@ def lanes3(env11):
 
 def test_matvec_batch_lanes_bitexact(lanes3):
     """With lanes on, a batch of >= 32 vectors runs as concurrent lanes (one host thread, HIP stream and workspace
-    per lane, hec_engine.hip matvec_lanes): 48 columns -> 3 lanes of 16; every output equals the oracle's."""
+    per lane, hec_matvec.hip matvec_lanes): 48 columns -> 3 lanes of 16; every output equals the oracle's."""
     e = lanes3
     n = 10
     A = [e.enc(seed=3000 + j) for j in range(n)]
